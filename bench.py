@@ -11,10 +11,14 @@ forms are timed beside it. Forced lengths: stop bias -1e4 and
 max_decoder_steps_i = ceil(M_i / r), so every run does exactly the same work.
 
 Prints ONE JSON line (rank 0). ``value`` = mel frames produced per second by the whole
-pipeline over all ranks, ids and waveforms resident in HBM (r = 2). Extra fields:
-Tacotron2-only frames/s, end-to-end RTF, ``e2e_rtf_host`` (ids on the host -> per-utterance
-waveforms on the host), the r = 1 run (``r1``), and ``roofline.pipeline_frac`` =
-SURVEY 8d's whole-pipeline bound / measured.
+pipeline over all ranks, ids and waveforms resident in HBM (r = 2); ``ms_per_step`` = the time of
+one timed step. A plain run does only that: set-up, ``--warmup`` steps, ``--steps`` timed steps, the
+line. ``--dump-outputs DIR`` also writes what the last timed step returned (dump_outputs).
+``--full`` adds every other measurement, each in passes of its own after the timed region: the
+blocking one-call and two-call forms, the event-timed stage split with Tacotron2-only frames/s,
+``e2e_rtf_host`` (ids on the host -> per-utterance waveforms on the host), the fp32-MFMA
+re-timing, the r = 1 run (``r1``), ``roofline`` (``pipeline_frac`` = SURVEY 8d's whole-pipeline
+bound / measured) and the CPU baseline.
 Launch for N > 1: ``python bench.py --gpus N`` starts N ranks itself (torch.distributed.run as a
 child process, before any GPU call; launch_plan), or run it as the ranks of
 ``python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`` (WORLD_SIZE must equal N).
@@ -80,6 +84,32 @@ def latest_profile(name):
         return rounds[0]
     flat = os.path.join(ROOT, "profiles", name)
     return flat if os.path.exists(flat) else None
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(dirname, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """``--dump-outputs``: every array of ``arrays`` (name -> ndarray) as ``dirname/<name>.npy``,
+    float32 (float64 stays float64), at most ``budget`` bytes in all. Outputs that fit are written
+    whole; otherwise every array keeps the same fraction of its elements, a sorted sample of flat
+    indices drawn from RandomState(seed) (the same indices on every run of the same shapes), written
+    1-D. Returns name -> [shape, elements written]."""
+    os.makedirs(dirname, exist_ok=True)
+    arrs = {k: np.ascontiguousarray(v, dtype=np.float64 if np.asarray(v).dtype == np.float64 else np.float32)
+            for k, v in arrays.items()}
+    room = budget - 4096 * len(arrs)            # .npy headers
+    total = sum(a.nbytes for a in arrs.values())
+    rs = np.random.RandomState(seed)
+    wrote = {}
+    for k in sorted(arrs):
+        a = arrs[k]
+        if total > room:
+            n = int(a.size * (room / total))
+            a = a.ravel()[np.sort(rs.choice(a.size, n, replace=False))]
+        np.save(os.path.join(dirname, k + ".npy"), a)
+        wrote[k] = [list(arrs[k].shape), int(a.size)]
+    return wrote
 
 
 def build_models(device, seed=0):
@@ -271,9 +301,17 @@ def main(argv=None):
     ap.add_argument("--kernel-iters", type=int, default=50)
     ap.add_argument("--f32-steps", type=int, default=3, help="steps re-timed with fp32-MFMA GEMMs only (0: skip)")
     ap.add_argument("--r1-steps", type=int, default=3, help="steps timed at r=1 as extra fields (0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other measurement (blocking and two-call forms, "
+                         "stage split, host-to-host step, fp32-MFMA re-timing, r=1, roofline, CPU baseline); "
+                         "--cpu-seconds, --no-cpu-baseline, --kernel-iters, --f32-steps and --r1-steps apply to it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (rank 0)")
     ap.add_argument("--plan-only", action="store_true",
                     help="print this rank's shard of the global batch as one JSON line and exit (no GPU)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # before any torch.cuda call (not even device_count): become the launcher of N ranks if asked
     cmd = launch_plan(args.gpus, os.environ, argv)
@@ -331,6 +369,7 @@ def main(argv=None):
         return int(mel_lens.sum()), wav
 
     wav_host = {}
+    last_out = {}
 
     def host_step(steps):
         """IDs on the host -> waveforms on the host (SURVEY 8d e2e RTF; server/synthesizer.py:147,155-156):
@@ -353,7 +392,8 @@ def main(argv=None):
         inference_vocoded_submit -> tts_taco_mbmelgan_submit / _finish): batch i + 1 is submitted,
         its encoder and decode running beside batch i's vocoder (the library's second stream), before
         batch i's result is taken.
-        Every batch's waveforms are final (range flag checked) inside the caller's timed region."""
+        Every batch's waveforms are final (range flag checked) inside the caller's timed region.
+        With --dump-outputs the last batch's result and lengths are kept in ``last_out``."""
         frames = 0
         prev = None
         for _ in range(n):
@@ -363,7 +403,9 @@ def main(argv=None):
                 prev.result()
             prev = cur
         if prev is not None:
-            prev.result()
+            res = prev.result()
+            if args.dump_outputs:
+                last_out["result"], last_out["mel_lengths"] = res, np.array(taco.last_mel_lengths)
         return frames
 
     def timed_pipelined(steps, n):
@@ -394,15 +436,21 @@ def main(argv=None):
     from tts_amd._lib import get_engine
     eng = get_engine(dev)
 
-    def measure(r, steps_n, warmup, with_host):
-        """One configuration (reduction factor r): the timed device-resident step, the stage split,
-        the host-to-host step, and the decoder launch statistics."""
+    def headline(r, steps_n, warmup):
+        """The timed region of one configuration (reduction factor r): warm-up, then ``steps_n``
+        pipelined steps."""
         taco.decoder.set_r(r)
         steps = forced_steps([M_all[i] for i in mine], r)
         for _ in range(warmup):
             one_step(steps)
         pipelined(steps, 2)
         ms, per_frames = timed_pipelined(steps, steps_n)
+        return {"ms": ms, "frames": per_frames, "steps": steps}
+
+    def extras(res, r, steps_n, with_host):
+        """--full, after ``headline``: the blocking forms, the stage split, the host-to-host step and
+        the decoder launch statistics, each in passes of its own."""
+        steps = res["steps"]
         sync_ms, _ = timed(lambda: one_step(steps), steps_n)  # one synchronous fused call per batch
         two_ms, _ = timed(lambda: one_step(steps, two_calls=True), steps_n)  # the reference's two-call form
         tt.clear()
@@ -410,8 +458,8 @@ def main(argv=None):
         for _ in range(2):  # per-stage split (separate, event-timed passes after the timed region)
             one_step(steps, True)
         path, launches = eng.decoder_stats()
-        res = {"ms": ms, "sync_ms": sync_ms, "two_call_ms": two_ms, "frames": per_frames, "steps": steps, "taco_ms": float(np.median(tt)),
-               "voc_ms": float(np.median(tv)), "path": path, "launches": launches}
+        res.update({"sync_ms": sync_ms, "two_call_ms": two_ms, "taco_ms": float(np.median(tt)),
+                    "voc_ms": float(np.median(tv)), "path": path, "launches": launches})
         if with_host:
             host_step(steps)
             res["host_ms"], _ = timed(lambda: host_step(steps), steps_n)
@@ -420,14 +468,70 @@ def main(argv=None):
         res.update(bound_ms=bound, dec_bound_ms=dec_bound, bound_x3_ms=bound_x3)
         return res
 
+    def measure(r, steps_n, warmup, with_host):
+        return extras(headline(r, steps_n, warmup), r, steps_n, with_host)
+
     r = args.r
-    m2 = measure(r, args.steps, args.warmup, with_host=True)
+    m2 = headline(r, args.steps, args.warmup)
     ms_step, per_step_frames, steps = m2["ms"], m2["frames"], m2["steps"]
     value = per_step_frames / (ms_step / 1000.0)
     audio_s = per_step_frames * HOP / SAMPLE_RATE
+    gemm_mode, fallbacks = eng.gemm_mode()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        names = ("decoder_outputs", "postnet_outputs", "alignments", "stop_tokens", "waveforms")
+        arrays = {k: v.cpu().numpy() for k, v in zip(names, last_out["result"])}
+        arrays["mel_lengths"] = last_out["mel_lengths"].astype(np.float64)
+        dumped = dump_outputs(args.dump_outputs, arrays)
+    last_out.clear()
+    out = {
+        "metric": "mel-frames/s (Tacotron2-DDC + MB-MelGAN end-to-end)",
+        "value": round(value, 1),
+        "unit": "mel-frames/s",
+        "n_gpus": world,
+        "rccl_world": dist.get_world_size() if world > 1 else 1,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_step, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "gemm": ("split-f16 MFMA, fp32-accurate (split16.h: 3 f16 products per fp32 product, fp32 accumulate)"
+                 if gemm_mode == "x3" else "fp32 MFMA"),
+        "x3_range_fallbacks": fallbacks,
+        "data": "synthetic (LJ-profile lengths, RandomState(0) ids, seeded random weights, forced length)",
+        "config": bench_config(world, args.per_gpu_batch, r),
+        "e2e_rtf": ms_step / 1000.0 / audio_s,
+        "entry": "Tacotron2.inference_vocoded_submit -> tts_taco_mbmelgan_submit / _finish, the host one batch "
+                 "ahead (batch i+1's Tacotron2 beside batch i's vocoder on the library's second stream)",
+        "full": bool(args.full),
+    }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
+    if args.full:
+        out.update(full_measurements(args, m2, extras, measure, timed_pipelined, one_step, eng, taco, world,
+                                     mine, my_T, gemm_mode))
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(tsd, vsd, tcfg, vcfg, ids, forced_steps(M_prof, r), r,
+                                               args.cpu_seconds)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+    return 0
+
+
+def full_measurements(args, m2, extras, measure, timed_pipelined, one_step, eng, taco, world, mine, my_T,
+                      gemm_mode):
+    """--full: everything the line reports beyond the headline, measured after the timed region.
+    Returns the extra fields of the line."""
+    r = args.r
+    extras(m2, r, args.steps, with_host=True)
+    ms_step, per_step_frames, steps = m2["ms"], m2["frames"], m2["steps"]
     taco_ms, voc_ms = m2["taco_ms"], m2["voc_ms"]
     my_frames = int(sum(s_ * r for s_ in steps))
-    gemm_mode, fallbacks = eng.gemm_mode()
     path, launches = m2["path"], m2["launches"]
 
     # the same step with every GEMM on the fp32 MFMA (no split-f16 kernels), for comparison
@@ -558,34 +662,14 @@ def main(argv=None):
         roof["decoder_frac"] = round(m2["dec_bound_ms"] / dec_ms, 4)
 
     host_audio = per_step_frames * HOP / SAMPLE_RATE
-    out = {
-        "metric": "mel-frames/s (Tacotron2-DDC + MB-MelGAN end-to-end)",
-        "value": round(value, 1),
-        "unit": "mel-frames/s",
-        "n_gpus": world,
-        "rccl_world": dist.get_world_size() if world > 1 else 1,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_step, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "gemm": ("split-f16 MFMA, fp32-accurate (split16.h: 3 f16 products per fp32 product, fp32 accumulate)"
-                 if gemm_mode == "x3" else "fp32 MFMA"),
+    return {
         "f32_gemm_ms_per_step": None if f32_ms is None else round(f32_ms, 3),
-        "x3_range_fallbacks": fallbacks,
-        "data": "synthetic (LJ-profile lengths, RandomState(0) ids, seeded random weights, forced length)",
-        "config": bench_config(world, args.per_gpu_batch, r),
-        "e2e_rtf": ms_step / 1000.0 / audio_s,
         "e2e_rtf_host": m2["host_ms"] / 1000.0 / host_audio,
         "host_ms_per_step": round(m2["host_ms"], 3),
         "sync_call_ms_per_step": round(m2["sync_ms"], 3),
         "two_call_ms_per_step": round(m2["two_call_ms"], 3),
-        "entry": "Tacotron2.inference_vocoded_submit -> tts_taco_mbmelgan_submit / _finish, the host one batch "
-                 "ahead (batch i+1's Tacotron2 beside batch i's vocoder on the library's second stream); sync_call_ms_per_step: one blocking "
-                 "tts_taco_mbmelgan_infer per batch; two_call_ms_per_step: Tacotron2.inference + "
-                 "MultibandMelganGenerator.inference",
+        "entry_forms": "sync_call_ms_per_step: one blocking tts_taco_mbmelgan_infer per batch; "
+                       "two_call_ms_per_step: Tacotron2.inference + MultibandMelganGenerator.inference",
         "tacotron2_mel_frames_per_s": round(my_frames / (taco_ms / 1000.0) * world, 1),
         "tacotron2_ms": round(taco_ms, 3),
         "vocoder_ms": round(voc_ms, 3),
@@ -595,15 +679,6 @@ def main(argv=None):
         "roofline": roof,
         "r1": other,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(tsd, vsd, tcfg, vcfg, ids, forced_steps(M_prof, r), r,
-                                           args.cpu_seconds)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
-    return 0
 
 
 if __name__ == "__main__":

@@ -219,6 +219,34 @@ def test_bench_gpus_2_starts_two_ranks_plan_only():
     assert bad.returncode != 0 and "WORLD_SIZE=3" in bad.stderr
 
 
+def test_bench_dump_outputs_whole_and_sampled(tmp_path):
+    """bench.py --dump-outputs: outputs that fit the byte budget are written whole as float32 (float64
+    kept); larger ones as the same seeded sample of every array on every run, within the budget."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    rs = np.random.RandomState(3)
+    arrays = {"a": rs.randn(7, 33, 5), "b": rs.randn(1001).astype(np.float32), "n": np.arange(9, dtype=np.int64)}
+    arrays["a"] = arrays["a"].astype(np.float64)
+    wrote = bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "whole" / f"{k}.npy")
+        assert got.dtype == (np.float64 if k == "a" else np.float32) and got.shape == v.shape
+        np.testing.assert_array_equal(got, v.astype(got.dtype))
+        assert wrote[k] == [list(v.shape), v.size]
+    budget = 3 * 4096 + 4000
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), arrays, budget=budget)
+    size = 0
+    for k, v in arrays.items():
+        g1, g2 = np.load(tmp_path / "s1" / f"{k}.npy"), np.load(tmp_path / "s2" / f"{k}.npy")
+        np.testing.assert_array_equal(g1, g2)
+        assert g1.ndim == 1 and 0 < g1.size < v.size and np.isin(g1, v.astype(g1.dtype)).all()
+        size += os.path.getsize(tmp_path / "s1" / f"{k}.npy")
+    assert size <= budget
+    assert bench.DUMP_BUDGET_BYTES <= 64 * 1000 * 1000
+
+
 def _pool_factory(seed, device):
     """GpuPool stand-in runner for the CPU suite: the oracle decode, tagged with the worker's device."""
     import sys

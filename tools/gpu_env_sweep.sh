@@ -3,15 +3,16 @@
 # Each round runs the default, then every configuration; prints ms_per_step, decoder step, tacotron2, vocoder.
 set -o pipefail
 cd "$(dirname "$0")/.."
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}  # where the logs and records go
+mkdir -p $OUT
 export TMPDIR=/tmp
 rounds=$1; shift
 bl() { python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(d['ms_per_step'], d['decoder_step_us'], d['tacotron2_ms'], d['vocoder_ms'])" $1; }
 for i in $(seq 1 $rounds); do
-  timeout -k 10 200 python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline --r1-steps 0 --f32-steps 0 > gpurun_out/sw.json 2>/dev/null || exit 1
-  echo "default run $i: $(bl gpurun_out/sw.json)"
+  timeout -k 10 200 python3 bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --r1-steps 0 --f32-steps 0 > $OUT/sw.json 2>/dev/null || exit 1
+  echo "default run $i: $(bl $OUT/sw.json)"
   for c in "$@"; do
-    env $c timeout -k 10 200 python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline --r1-steps 0 --f32-steps 0 > gpurun_out/sw.json 2>/dev/null || exit 1
-    echo "[$c] run $i: $(bl gpurun_out/sw.json)"
+    env $c timeout -k 10 200 python3 bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --r1-steps 0 --f32-steps 0 > $OUT/sw.json 2>/dev/null || exit 1
+    echo "[$c] run $i: $(bl $OUT/sw.json)"
   done
 done

@@ -3,15 +3,16 @@
 # switch, same box: tools/gpu_lstm_env.sh <rounds> VAR=value
 set -o pipefail
 cd "$(dirname "$0")/.."
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}  # where the logs and records go
+mkdir -p $OUT
 export TMPDIR=/tmp
 rounds=$1; shift
 for i in $(seq 1 $rounds); do
   for v in default env; do
-    rm -rf gpurun_out/le_prof
+    rm -rf $OUT/le_prof
     if [ $v = env ]; then pre="env $*"; else pre=""; fi
-    $pre timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/le_prof -o run --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --r1-steps 0 --f32-steps 0 > gpurun_out/le_prof.log 2>&1 || exit 1
-    f=$(find gpurun_out/le_prof -name "*kernel_stats.csv" | head -1)
+    $pre timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/le_prof -o run --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --r1-steps 0 --f32-steps 0 > $OUT/le_prof.log 2>&1 || exit 1
+    f=$(find $OUT/le_prof -name "*kernel_stats.csv" | head -1)
     echo "$v run $i: $(python3 -c "
 import csv,sys
 for r in csv.DictReader(open(sys.argv[1])):
