@@ -1,0 +1,540 @@
+// Glow-TTS: weight packing, encoder + durations, flow decoder, and the tts_glow_* entry points.
+#include "host.h"
+
+#include <cmath>
+#include <cstdlib>
+
+using namespace ttsh;
+
+namespace {
+
+// rows (r, half + r) -> (2r, 2r + 1) of a (2 * half, rowlen) weight and its bias
+std::pair<std::vector<float>, std::vector<float>> interleave_halves(const std::vector<float>& w,
+                                                                           const std::vector<float>& b, int half,
+                                                                           int rowlen) {
+  std::vector<float> wo(w.size()), bo(b.size());
+  for (int r = 0; r < 2 * half; ++r) {
+    const int src = (r & 1) ? half + r / 2 : r / 2;
+    std::copy(w.begin() + (size_t)src * rowlen, w.begin() + (size_t)(src + 1) * rowlen, wo.begin() + (size_t)r * rowlen);
+    bo[r] = b[src];
+  }
+  return {wo, bo};
+}
+
+void glow_finalize(tts_ctx* c, int num_chars, int enc_layers, int flows, int wn_layers) {
+  auto& G = c->glow;
+  const auto& h = c->glow_host;
+  G.ready = false;
+  const int H = G.H, C = G.C, F = G.Fdp, C2 = 2 * C;
+  TTS_CHECK(enc_layers >= 1 && enc_layers <= 32 && flows >= 1 && flows <= 32 && wn_layers >= 1 && wn_layers <= 8,
+            "glow: layer counts");
+  G.num_chars = num_chars;
+  G.enc_layers = enc_layers;
+  G.flows = flows;
+  G.wn_layers = wn_layers;
+  int p2[8] = {2}, p1[8] = {1}, p0[8] = {0};
+  {
+    auto e = need(h, "encoder.emb.weight", {num_chars, H}).d;
+    const float sc = std::sqrt((float)H);  // encoder.py:107, x * math.sqrt(hidden) in fp32
+    for (auto& v : e) v *= sc;
+    G.emb.upload(e);
+  }
+  G.enc_conv.clear();
+  G.enc_g.clear();
+  G.enc_b.clear();
+  G.tdsep = h.count("encoder.encoder.layers.0.time_conv.weight") > 0;
+  G.tfm = h.count("encoder.encoder.attn_layers.0.conv_q.weight") > 0;
+  if (G.tdsep || G.tfm) {
+    G.pre_conv.clear();
+    G.pre_conv.resize(3);
+    G.pre_g.clear();
+    G.pre_g.resize(3);
+    G.pre_b.clear();
+    G.pre_b.resize(3);
+    for (int i = 0; i < 3; ++i) {
+      const std::string q = "encoder.pre.";
+      pack_conv(G.pre_conv[i], need(h, q + "conv_layers." + std::to_string(i) + ".weight", {H, H, 5}).d,
+                need(h, q + "conv_layers." + std::to_string(i) + ".bias", {H}).d, H, H, 5, 1, 1, p2);
+      G.pre_g[i].upload(need(h, q + "norm_layers." + std::to_string(i) + ".gamma", {1, H, 1}).d);
+      G.pre_b[i].upload(need(h, q + "norm_layers." + std::to_string(i) + ".beta", {1, H, 1}).d);
+    }
+    pack_conv(G.pre_proj, need(h, "encoder.pre.proj.weight", {H, H, 1}).d, need(h, "encoder.pre.proj.bias", {H}).d, H,
+              H, 1, 1, 1, p0);
+  }
+  if (G.tfm) {  // transformer.py:265-319, num_layers = enc_layers
+    for (auto* v : {&G.tfm_qkv, &G.tfm_o, &G.tfm_f1, &G.tfm_f2}) {
+      v->clear();
+      v->resize(enc_layers);
+    }
+    for (auto* v : {&G.tfm_g1, &G.tfm_b1, &G.tfm_g2, &G.tfm_b2}) {
+      v->clear();
+      v->resize(enc_layers);
+    }
+    const int Fc = 768;
+    for (int i = 0; i < enc_layers; ++i) {
+      const std::string a = "encoder.encoder.attn_layers." + std::to_string(i) + ".";
+      std::vector<float> wqkv, bqkv;
+      for (const char* n : {"q", "k", "v"}) {
+        const auto& w = need(h, a + "conv_" + n + ".weight", {H, H, 1}).d;
+        const auto& bb = need(h, a + "conv_" + n + ".bias", {H}).d;
+        wqkv.insert(wqkv.end(), w.begin(), w.end());
+        bqkv.insert(bqkv.end(), bb.begin(), bb.end());
+      }
+      pack_conv(G.tfm_qkv[i], wqkv, bqkv, H, 3 * H, 1, 1, 1, p0);
+      pack_conv(G.tfm_o[i], need(h, a + "conv_o.weight", {H, H, 1}).d, need(h, a + "conv_o.bias", {H}).d, H, H, 1, 1,
+                1, p0);
+      const std::string f = "encoder.encoder.ffn_layers." + std::to_string(i) + ".";
+      pack_conv(G.tfm_f1[i], need(h, f + "conv_1.weight", {Fc, H, 3}).d, need(h, f + "conv_1.bias", {Fc}).d, H, Fc, 3,
+                1, 1, p1);
+      pack_conv(G.tfm_f2[i], need(h, f + "conv_2.weight", {H, Fc, 3}).d, need(h, f + "conv_2.bias", {H}).d, Fc, H, 3,
+                1, 1, p1);
+      const std::string n1 = "encoder.encoder.norm_layers_1." + std::to_string(i) + ".";
+      const std::string n2 = "encoder.encoder.norm_layers_2." + std::to_string(i) + ".";
+      G.tfm_g1[i].upload(need(h, n1 + "gamma", {1, H, 1}).d);
+      G.tfm_b1[i].upload(need(h, n1 + "beta", {1, H, 1}).d);
+      G.tfm_g2[i].upload(need(h, n2 + "gamma", {1, H, 1}).d);
+      G.tfm_b2[i].upload(need(h, n2 + "beta", {1, H, 1}).d);
+    }
+  }
+  if (G.tdsep) {
+    // eval BatchNorm: y = (x - mean) * w / sqrt(var + 1e-5) + b, folded in double
+    auto bn_fold = [&](const std::string& name, int n, std::vector<float>& W, std::vector<float>& bias, int rowlen) {
+      const auto& w = need(h, name + ".weight", {n}).d;
+      const auto& bb = need(h, name + ".bias", {n}).d;
+      const auto& mu = need(h, name + ".running_mean", {n}).d;
+      const auto& var = need(h, name + ".running_var", {n}).d;
+      for (int r = 0; r < n; ++r) {
+        const double sc = (double)w[r] / std::sqrt((double)var[r] + 1e-5);
+        for (int k = 0; k < rowlen; ++k) W[(size_t)r * rowlen + k] = (float)(W[(size_t)r * rowlen + k] * sc);
+        bias[r] = (float)(((double)bias[r] - mu[r]) * sc + bb[r]);
+      }
+    };
+    G.tds_tc.clear();
+    G.tds_tc.resize(enc_layers);
+    G.tds_tc2.clear();
+    G.tds_tc2.resize(enc_layers);
+    G.tds_dw.clear();
+    G.tds_dw.resize(enc_layers);
+    G.tds_dwb.clear();
+    G.tds_dwb.resize(enc_layers);
+    for (int i = 0; i < enc_layers; ++i) {
+      const std::string q = "encoder.encoder.layers." + std::to_string(i) + ".";
+      auto w1 = need(h, q + "time_conv.weight", {2 * H, H, 1}).d;
+      auto b1 = need(h, q + "time_conv.bias", {2 * H}).d;
+      bn_fold(q + "norm1", 2 * H, w1, b1, H);
+      auto [w1i, b1i] = interleave_halves(w1, b1, H, H);  // (a_c, g_c) pairs for the GLU epilogue
+      pack_conv(G.tds_tc[i], w1i, b1i, H, 2 * H, 1, 1, 1, p0);
+      auto wd = need(h, q + "depth_conv.weight", {H, 1, 5}).d;
+      auto bd = need(h, q + "depth_conv.bias", {H}).d;
+      bn_fold(q + "norm2", H, wd, bd, 5);
+      G.tds_dw[i].upload(wd);
+      G.tds_dwb[i].upload(bd);
+      auto w2 = need(h, q + "time_conv2.weight", {H, H, 1}).d;
+      auto b2 = need(h, q + "time_conv2.bias", {H}).d;
+      bn_fold(q + "norm3", H, w2, b2, H);
+      pack_conv(G.tds_tc2[i], w2, b2, H, H, 1, 1, 1, p0);
+    }
+  }
+  const bool gated = !G.tdsep && !G.tfm;
+  G.enc_conv.resize(gated ? enc_layers : 0);
+  G.enc_g.resize(gated ? enc_layers : 0);
+  G.enc_b.resize(gated ? enc_layers : 0);
+  for (int i = 0; i < (gated ? enc_layers : 0); ++i) {
+    const std::string pf = "encoder.encoder.";
+    pack_conv(G.enc_conv[i], need(h, pf + "conv_layers." + std::to_string(i) + ".weight", {2 * H, H, 5}).d,
+              need(h, pf + "conv_layers." + std::to_string(i) + ".bias", {2 * H}).d, H, 2 * H, 5, 1, 1, p2);
+    G.enc_g[i].upload(need(h, pf + "norm_layers." + std::to_string(i) + ".gamma", {1, 2 * H, 1}).d);
+    G.enc_b[i].upload(need(h, pf + "norm_layers." + std::to_string(i) + ".beta", {1, 2 * H, 1}).d);
+  }
+  pack_conv(G.proj_m, need(h, "encoder.proj_m.weight", {C, H, 1}).d, need(h, "encoder.proj_m.bias", {C}).d, H, C, 1, 1,
+            1, p0);
+  const std::string dp = "encoder.duration_predictor.";
+  {
+    auto it = h.find(dp + "conv_1.weight");
+    TTS_CHECK(it != h.end() && it->second.shape.size() == 3, "missing tensor: " + dp + "conv_1.weight");
+    G.c_in = (int)it->second.shape[1] - H;
+    TTS_CHECK(G.c_in >= 0 && G.c_in <= 4096, "glow: duration predictor input channels");
+  }
+  const int cin = G.c_in, cpad = (cin + 15) / 16 * 16;
+  G.c_pad = cpad;
+  {
+    // [x; g] input of conv_1, g's channels zero-padded to c_pad
+    const auto& w = need(h, dp + "conv_1.weight", {F, H + cin, 3}).d;
+    std::vector<float> wp((size_t)F * (H + cpad) * 3, 0.f);
+    for (int o = 0; o < F; ++o)
+      std::copy(w.begin() + (size_t)o * (H + cin) * 3, w.begin() + (size_t)(o + 1) * (H + cin) * 3,
+                wp.begin() + (size_t)o * (H + cpad) * 3);
+    pack_conv(G.dp1, wp, need(h, dp + "conv_1.bias", {F}).d, H + cpad, F, 3, 1, 1, p1);
+  }
+  G.n_spk = 0;
+  G.emb_g.reset();
+  if (h.count("emb_g.weight")) {
+    auto it = h.find("emb_g.weight");
+    TTS_CHECK(it->second.shape.size() == 2 && it->second.shape[1] == cin && it->second.shape[0] >= 1,
+              "glow: emb_g.weight must be (num_speakers, c_in_channels)");
+    G.n_spk = (int)it->second.shape[0];
+    if (cin > 0) G.emb_g.upload(it->second.d);
+  }
+  pack_conv(G.dp2, need(h, dp + "conv_2.weight", {F, F, 3}).d, need(h, dp + "conv_2.bias", {F}).d, F, F, 3, 1, 1, p1);
+  pack_conv(G.dp_proj, need(h, dp + "proj.weight", {1, F, 1}).d, need(h, dp + "proj.bias", {1}).d, F, 1, 1, 1, 1, p0);
+  G.dp_g1.upload(need(h, dp + "norm_1.gamma", {1, F, 1}).d);
+  G.dp_b1.upload(need(h, dp + "norm_1.beta", {1, F, 1}).d);
+  G.dp_g2.upload(need(h, dp + "norm_2.gamma", {1, F, 1}).d);
+  G.dp_b2.upload(need(h, dp + "norm_2.beta", {1, F, 1}).d);
+  G.start.clear();
+  G.start.resize(flows);
+  G.end.clear();
+  G.end.resize(flows);
+  G.invtab.clear();
+  G.invtab.resize(flows);
+  G.wn_in.clear();
+  G.wn_in.resize(flows * wn_layers);
+  G.wn_rs.clear();
+  G.wn_rs.resize(flows * wn_layers);
+  std::vector<float> cond_w(cin > 0 ? (size_t)flows * wn_layers * 2 * H * cpad : 0, 0.f);
+  std::vector<float> cond_b(cin > 0 ? (size_t)flows * wn_layers * 2 * H : 0, 0.f);
+  for (int k = 0; k < flows; ++k) {
+    const std::string an = "decoder.flows." + std::to_string(3 * k) + ".";
+    const std::string ic = "decoder.flows." + std::to_string(3 * k + 1) + ".";
+    const std::string cp = "decoder.flows." + std::to_string(3 * k + 2) + ".";
+    pack_conv(G.start[k], wn_weight(h, cp + "start", {H, C, 1}), need(h, cp + "start.bias", {H}).d, C, H, 1, 1, 1, p0);
+    // end rows interleaved (m_c, logs_c) for the conv's coupling-pair epilogue
+    auto [we, be] = interleave_halves(need(h, cp + "end.weight", {C2, H, 1}).d, need(h, cp + "end.bias", {C2}).d, C, H);
+    pack_conv(G.end[k], we, be, H, C2, 1, 1, 1, p0);
+    for (int i = 0; i < wn_layers; ++i) {
+      const std::string wi = cp + "wn.in_layers." + std::to_string(i);
+      const std::string wr = cp + "wn.res_skip_layers." + std::to_string(i);
+      // in rows interleaved (tanh_c, sigmoid_c) for the gate-pair epilogue
+      auto [wg, bg] = interleave_halves(wn_weight(h, wi, {2 * H, H, 5}), need(h, wi + ".bias", {2 * H}).d, H, H * 5);
+      pack_conv(G.wn_in[k * wn_layers + i], wg, bg, H, 2 * H, 5, 1, 1, p2);
+      // rows [0, H): residual, [H, 2H): skip -- one conv into the [hidden | skip] buffer; the last
+      // layer has the skip rows only
+      const int rsc = i == wn_layers - 1 ? H : 2 * H;
+      pack_conv(G.wn_rs[k * wn_layers + i], wn_weight(h, wr, {rsc, H, 1}), need(h, wr + ".bias", {rsc}).d, H, rsc, 1,
+                1, 1, p0);
+    }
+    if (cin > 0) {  // cond_layer (2H * wn_layers, c_in): per layer slice interleaved like wn_in
+      const int L2 = 2 * H * wn_layers;
+      const auto w = wn_weight(h, cp + "wn.cond_layer", {L2, cin, 1});
+      const auto& cb = need(h, cp + "wn.cond_layer.bias", {L2}).d;
+      for (int i = 0; i < wn_layers; ++i) {
+        std::vector<float> wl(w.begin() + (size_t)i * 2 * H * cin, w.begin() + (size_t)(i + 1) * 2 * H * cin);
+        std::vector<float> bl(cb.begin() + (size_t)i * 2 * H, cb.begin() + (size_t)(i + 1) * 2 * H);
+        auto [wi, bi] = interleave_halves(wl, bl, H, cin);
+        const size_t r0 = ((size_t)k * wn_layers + i) * 2 * H;
+        for (int r = 0; r < 2 * H; ++r) {
+          std::copy(wi.begin() + (size_t)r * cin, wi.begin() + (size_t)(r + 1) * cin,
+                    cond_w.begin() + (r0 + r) * cpad);
+          cond_b[r0 + r] = bi[r];
+        }
+      }
+    }
+    // reverse of [ActNorm, InvConvNear] (glow.py:48-58, 184-201): output channel c' = i*C + 2j + k
+    // (split s' = 2i + k) = (sum_s winv[s'][s] x[c_s] - bias[c']) * exp(-logs[c']), c_s = i_s*C + 2j + k_s
+    const auto& w4 = need(h, ic + "weight", {4, 4}).d;
+    double a[4][8];
+    for (int r = 0; r < 4; ++r)
+      for (int q = 0; q < 8; ++q) a[r][q] = q < 4 ? w4[r * 4 + q] : (q - 4 == r ? 1.0 : 0.0);
+    for (int col = 0; col < 4; ++col) {  // Gauss-Jordan with partial pivoting
+      int piv = col;
+      for (int r = col + 1; r < 4; ++r)
+        if (std::fabs(a[r][col]) > std::fabs(a[piv][col])) piv = r;
+      for (int q = 0; q < 8; ++q) std::swap(a[col][q], a[piv][q]);
+      TTS_CHECK(std::fabs(a[col][col]) > 1e-12, "glow: singular InvConvNear weight");
+      const double d = a[col][col];
+      for (int q = 0; q < 8; ++q) a[col][q] /= d;
+      for (int r = 0; r < 4; ++r)
+        if (r != col) {
+          const double f = a[r][col];
+          for (int q = 0; q < 8; ++q) a[r][q] -= f * a[col][q];
+        }
+    }
+    // the reference inverts in fp32 and casts (glow.py:190-193): round the inverse to float
+    const auto& logs = need(h, an + "logs", {1, C2, 1}).d;
+    const auto& abias = need(h, an + "bias", {1, C2, 1}).d;
+    std::vector<float> tab((size_t)C2 * 6);
+    for (int cp2 = 0; cp2 < C2; ++cp2) {
+      const int s2 = 2 * (cp2 / C) + cp2 % 2;
+      for (int s1 = 0; s1 < 4; ++s1) tab[cp2 * 6 + s1] = (float)a[s2][4 + s1];
+      tab[cp2 * 6 + 4] = abias[cp2];
+      tab[cp2 * 6 + 5] = std::exp(-logs[cp2]);
+    }
+    G.invtab[k].upload(tab);
+  }
+  if (cin > 0) pack_conv(G.cond, cond_w, cond_b, cpad, flows * wn_layers * 2 * H, 1, 1, 1, p0);
+  HIP_OK(hipDeviceSynchronize());
+  G.ready = true;
+}
+
+// encoder + duration predictor + durations: h_ylens out (per-utterance frames)
+void glow_encode(tts_ctx* c, const int64_t* d_ids, const int32_t* h_lens, const int32_t* h_spk, int B, int T,
+                 float length_scale, int32_t* h_ylens) {
+  auto& G = c->glow;
+  auto& W = c->glws;
+  TTS_CHECK(G.ready, "glow weights not finalized");
+  TTS_CHECK(B >= 1 && B <= 64 && T >= 1 && T <= 4096, "glow: bad sizes");
+  for (int b = 0; b < B; ++b) TTS_CHECK(h_lens[b] >= 1 && h_lens[b] <= T, "glow: lens out of range");
+  if (h_spk) {
+    // the reference looks g up in emb_g (absent unless num_speakers > 1) and feeds it to every WN
+    // cond_layer (absent unless c_in_channels > 0): glow_tts.py:160, glow.py:119-120
+    TTS_CHECK(G.n_spk > 1, "glow: speaker ids given but the model has no emb_g (num_speakers <= 1)");
+    TTS_CHECK(G.c_in > 0, "glow: speaker ids given but the model has no cond_layer (c_in_channels = 0)");
+    for (int b = 0; b < B; ++b) TTS_CHECK(h_spk[b] >= 0 && h_spk[b] < G.n_spk, "glow: speaker id out of range");
+  } else {
+    // without g the reference's duration predictor reads x alone (encoder.py:136), which its
+    // conv_1 rejects when it was built for hidden + c_in_channels inputs
+    TTS_CHECK(G.c_in == 0, "glow: this model's duration predictor expects speaker conditioning (c_in_channels > 0)");
+  }
+  hipStream_t s = c->s;
+  const int H = G.H, C = G.C, F = G.Fdp;
+  long gen = 0;
+  grow<int>(W.lens, 64, gen);
+  grow<int>(W.ylens, 64, gen);
+  grow<int>(W.klens, 64, gen);
+  grow<float>(W.xa, (size_t)B * 2 * H * T, gen);
+  grow<float>(W.xb, (size_t)B * H * T, gen);
+  grow<float>(W.h2, (size_t)B * 2 * H * T, gen);
+  grow<float>(W.hdp, (size_t)B * F * T, gen);
+  grow<float>(W.logw, (size_t)B * T, gen);
+  grow<float>(W.cum, (size_t)B * T, gen);
+  grow<float>(W.wceil, (size_t)B * T, gen);
+  grow<float>(W.om, (size_t)B * C * T, gen);
+  if (G.tfm) grow<float>(W.big, (size_t)B * 768 * T, gen);
+  W.B = B;
+  W.Tx = T;
+  W.has_g = h_spk != nullptr;
+  std::vector<int> lens(h_lens, h_lens + B);
+  HIP_OK(hipMemcpyAsync(W.lens.p, lens.data(), B * 4, hipMemcpyHostToDevice, s));
+  const int* dl = W.lens.i();
+  if (W.has_g) {
+    // g, then every WN layer's gate bias cond_layer(g) as one (B, flows * wn_layers * 2H) 1x1 conv
+    // over a length-1 sequence
+    const int NC = G.flows * G.wn_layers * 2 * H;
+    grow<int>(W.spk, 64, gen);
+    grow<float>(W.g, (size_t)B * G.c_pad, gen);
+    grow<float>(W.gcond, (size_t)B * NC, gen);
+    if (!W.ones.p) {
+      std::vector<int> one(64, 1);
+      W.ones.upload(one);
+    }
+    W.h_spk.assign(h_spk, h_spk + B);
+    HIP_OK(hipMemcpyAsync(W.spk.p, W.h_spk.data(), B * 4, hipMemcpyHostToDevice, s));
+    launch_glow_speaker(W.spk.i(), G.emb_g.f(), G.c_in, G.c_pad, W.g.f(), B, s);
+    ConvCall cc;
+    cc.lens = W.ones.i();
+    cc.B = B;
+    cc.oflow = x3_flag(c);
+    cc.max_q = 1;
+    cc.s[0] = src_of(W.g.f(), G.c_pad, 1, 1, G.c_pad, 0);
+    cc.out = W.gcond.f();
+    cc.ob = NC;
+    cc.oc = 1;
+    cc.ot = 1;
+    run_conv(G.cond, cc, s);
+  }
+  float* x = W.xa.f();   // (B, H, T) current activations
+  float* x2 = W.xb.f();  // ping-pong
+  launch_glow_embed(d_ids, T, G.emb.f(), G.num_chars, H, dl, x, B, s);
+  auto conv = [&](const ConvLayer& L, const float* in, int cin, float* out, int cout, int epi,
+                  const float* resid = nullptr) {
+    ConvCall cc;
+    cc.lens = dl;
+    cc.B = B;
+    cc.oflow = x3_flag(c);
+    cc.max_q = T;
+    cc.s[0] = src_of(in, (long)cin * T, T, 1, cin, 0);
+    cc.out = out;
+    cc.ob = (long)cout * T;
+    cc.oc = T;
+    cc.ot = 1;
+    cc.epi = epi;
+    cc.resid = resid;
+    cc.rb = (long)cout * T;
+    cc.rc = T;
+    cc.rt = 1;
+    run_conv(L, cc, s);
+  };
+  if (G.tdsep || G.tfm) {
+    // ConvLayerNorm prenet (glow.py:43-50): 3 x (conv k5 -> LayerNorm -> ReLU), x + proj(.)
+    float* h0 = W.h2.f();
+    float* h1 = W.hdp.f();
+    conv(G.pre_conv[0], x, H, h0, H, 0);
+    launch_ln(h0, (long)H * T, H, G.pre_g[0].f(), G.pre_b[0].f(), dl, B, T, s, true);
+    conv(G.pre_conv[1], h0, H, h1, H, 0);
+    launch_ln(h1, (long)H * T, H, G.pre_g[1].f(), G.pre_b[1].f(), dl, B, T, s, true);
+    conv(G.pre_conv[2], h1, H, h0, H, 0);
+    launch_ln(h0, (long)H * T, H, G.pre_g[2].f(), G.pre_b[2].f(), dl, B, T, s, true);
+    conv(G.pre_proj, h0, H, x2, H, 0, x);
+    std::swap(x, x2);
+    // Transformer (transformer.py:307-319): x = LN1(x + o(attn(x))), x = LN2(x + FFN(x))
+    for (int i = 0; i < (G.tfm ? G.enc_layers : 0); ++i) {
+      float* big = W.big.f();
+      conv(G.tfm_qkv[i], x, H, big, 3 * H, 0);
+      launch_glow_mha(big, H, H / 96, T, dl, h0, B, s);
+      conv(G.tfm_o[i], h0, H, x2, H, 0, x);
+      launch_ln(x2, (long)H * T, H, G.tfm_g1[i].f(), G.tfm_b1[i].f(), dl, B, T, s);
+      conv(G.tfm_f1[i], x2, H, big, 768, 1);
+      conv(G.tfm_f2[i], big, 768, x, H, 0, x2);
+      launch_ln(x, (long)H * T, H, G.tfm_g2[i].f(), G.tfm_b2[i].f(), dl, B, T, s);
+    }
+    // TimeDepthSeparableConvBlock (time_depth_sep_conv.py:51-63, 93-96)
+    for (int i = 0; i < (G.tdsep ? G.enc_layers : 0); ++i) {
+      conv(G.tds_tc[i], x, H, h0, H, 6);  // time_conv + BN + GLU -> H rows
+      launch_tds_depthwise(h0, H, T, G.tds_dw[i].f(), G.tds_dwb[i].f(), dl, h1, B, s);
+      conv(G.tds_tc2[i], h1, H, x2, H, 0, x);  // time_conv2 + BN + residual
+      std::swap(x, x2);
+    }
+  }
+  for (int i = 0; i < (G.tdsep || G.tfm ? 0 : G.enc_layers); ++i) {  // GatedConvBlock (gated_conv.py:31-42)
+    conv(G.enc_conv[i], x, H, W.h2.f(), 2 * H, 0);
+    launch_glu_ln_res(W.h2.f(), (long)2 * H * T, 2 * H, G.enc_g[i].f(), G.enc_b[i].f(), x, (long)H * T, x2,
+                      (long)H * T, dl, B, T, s);
+    std::swap(x, x2);
+  }
+  conv(G.proj_m, x, H, W.om.f(), C, 0);  // o_mean (encoder.py:125)
+  // DurationPredictor (duration_predictor.py:29-40): conv -> relu -> LN, twice, then proj; the
+  // input is [x; g] with g constant over time (encoder.py:131-135), masked like x by the conv
+  if (G.c_pad > 0) {
+    ConvCall cc;
+    cc.lens = dl;
+    cc.B = B;
+    cc.max_q = T;
+    cc.nsrc = 2;
+    cc.s[0] = src_of(x, (long)H * T, T, 1, H, 0);
+    cc.s[1] = src_of(W.g.f(), G.c_pad, 1, 0, G.c_pad, 0);
+    cc.out = W.hdp.f();
+    cc.ob = (long)F * T;
+    cc.oc = T;
+    cc.ot = 1;
+    cc.epi = 1;
+    // two sources: the fp32 conv (conv_x3 stages one source; this k3 conv over ~T x (H + c_pad)
+    // inputs is a few microseconds of the call either way)
+    run_conv(G.dp1, cc, s);
+  } else {
+    conv(G.dp1, x, H, W.hdp.f(), F, 1);
+  }
+  launch_ln(W.hdp.f(), (long)F * T, F, G.dp_g1.f(), G.dp_b1.f(), dl, B, T, s);
+  conv(G.dp2, W.hdp.f(), F, W.h2.f(), F, 1);
+  launch_ln(W.h2.f(), (long)F * T, F, G.dp_g2.f(), G.dp_b2.f(), dl, B, T, s);
+  conv(G.dp_proj, W.h2.f(), F, W.logw.f(), 1, 0);
+  launch_glow_durations(W.logw.f(), T, dl, length_scale, W.cum.f(), W.ylens.i(), W.wceil.f(), B, s);
+  HIP_OK(hipMemcpyAsync(h_ylens, W.ylens.p, B * 4, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  int mx = 1;
+  W.h_ylens.assign(h_ylens, h_ylens + B);
+  W.h_klens.resize(B);
+  for (int b = 0; b < B; ++b) mx = std::max(mx, (int)h_ylens[b]);
+  W.Ty = mx;
+}
+
+// expand + noise + reverse flows after glow_encode: d_y (B, 80, 2*(Ty/2)), d_ymean (B, 80, Ty),
+// d_attn (B, Ty, Tx), d_logw (B, Tx) = o_dur_log; d_noise (B, 80, Ty) standard normal or null
+void glow_decode(tts_ctx* c, const float* d_noise, float noise_scale, int Ty, float* d_y, float* d_ymean,
+                 float* d_attn, float* d_logw) {
+  auto& G = c->glow;
+  auto& W = c->glws;
+  TTS_CHECK(W.B > 0 && Ty == W.Ty, "glow: decode after encode with Ty = max(y_lengths)");
+  hipStream_t s = c->s;
+  const int B = W.B, Tx = W.Tx, H = G.H, C = G.C, C2 = 2 * C, K = Ty / 2;
+  long gen = 0;
+  const int K1 = std::max(K, 1);
+  grow<float>(W.z, (size_t)B * C * Ty, gen);
+  grow<float>(W.sq, (size_t)B * C2 * K1, gen);
+  grow<float>(W.sq2, (size_t)B * C2 * K1, gen);
+  grow<float>(W.whs, (size_t)B * 2 * H * K1, gen);
+  grow<float>(W.wacts, (size_t)B * H * K1, gen);
+  launch_glow_expand(W.om.f(), C, Tx, W.lens.i(), W.cum.f(), W.ylens.i(), Ty, d_noise, noise_scale, d_ymean, W.z.f(),
+                     d_attn, B, s);
+  HIP_OK(hipMemcpyAsync(d_logw, W.logw.p, (size_t)B * Tx * 4, hipMemcpyDeviceToDevice, s));
+  HIP_OK(hipMemsetAsync(d_y, 0, (size_t)B * C * 2 * K * 4, s));
+  if (K == 0) return;
+  // squeezed lengths floor(y_len / 2) (decoder.py:13-15); the staging vector lives in the
+  // workspace so the async copy never reads a dead host buffer
+  for (int b = 0; b < B; ++b) W.h_klens[b] = W.h_ylens[b] / 2;
+  HIP_OK(hipMemcpyAsync(W.klens.p, W.h_klens.data(), B * 4, hipMemcpyHostToDevice, s));
+  const int* kl = W.klens.i();
+  launch_glow_squeeze(W.z.f(), C, Ty, W.ylens.i(), W.sq.f(), K, B, s);
+  // every activation is (B, rows, K) with a per-buffer batch stride (in rows)
+  auto conv = [&](const ConvLayer& L, const float* in, int in_rows, float* out, int out_rows, const float* resid,
+                  int epi, int resid_rows = 0, const float* aux = nullptr) {
+    ConvCall cc;
+    cc.lens = kl;
+    cc.B = B;
+    cc.oflow = x3_flag(c);
+    cc.max_q = K;
+    cc.s[0] = src_of(in, (long)in_rows * K, K, 1, L.Cin, 0);
+    cc.out = out;
+    cc.ob = (long)out_rows * K;
+    cc.oc = K;
+    cc.ot = 1;
+    cc.resid = resid;
+    cc.rb = (long)out_rows * K;
+    cc.rc = K;
+    cc.rt = 1;
+    cc.epi = epi;
+    cc.resid_rows = resid_rows;
+    cc.aux = aux;
+    cc.auxb = (long)G.flows * G.wn_layers * 2 * H;  // epi 3: gcond's batch stride
+    run_conv(L, cc, s);
+  };
+  float* x = W.sq.f();
+  float* x2 = W.sq2.f();
+  float* hid = W.whs.f();                 // [hidden | skip] (B, 2H, K)
+  float* skip = W.whs.f() + (size_t)H * K;
+  for (int k = G.flows - 1; k >= 0; --k) {
+    // CouplingBlock reverse (glow.py:245-262): WN over start(x0), then z1 = (x1 - m) exp(-logs)
+    conv(G.start[k], x, C2, hid, 2 * H, nullptr, 0);
+    for (int i = 0; i < G.wn_layers; ++i) {  // WN (glow.py:118-138)
+      const int li = k * G.wn_layers + i;
+      // gate fused; with g, cond_layer(g)'s slice for this layer is a per-utterance gate bias
+      conv(G.wn_in[li], hid, 2 * H, W.wacts.f(), H, nullptr, 3, 0, W.has_g ? W.gcond.f() + (size_t)li * 2 * H : nullptr);
+      // skip rows start at the first layer's output (no accumulate), hidden rows add the residual
+      if (i < G.wn_layers - 1) conv(G.wn_rs[li], W.wacts.f(), H, hid, 2 * H, hid, 0, i == 0 ? H : 0);
+      else conv(G.wn_rs[li], W.wacts.f(), H, skip, 2 * H, i == 0 ? nullptr : skip, 0);
+    }
+    // end conv + coupling + inverse InvConvNear / ActNorm: reads x, writes the next x
+    conv(G.end[k], skip, 2 * H, x2, C2, x, 5, 0, G.invtab[k].f());
+    std::swap(x, x2);
+  }
+  launch_glow_unsqueeze(x, C2, K, W.ylens.i(), d_y, 2 * K, B, s);
+  HIP_OK(hipStreamSynchronize(s));
+}
+
+}  // namespace
+
+extern "C" {
+
+int tts_glow_set_tensor(tts_ctx* c, const char* name, const float* h, const int64_t* shape, int ndim) {
+  return stage_tensor(c, &tts_ctx::glow_host, name, h, shape, ndim);
+}
+
+int tts_glow_finalize(tts_ctx* c, int num_chars, int enc_layers, int num_flow_blocks, int num_block_layers) {
+  return guarded_ctx(c, [&] {
+    DeviceGuard g(c->device);
+    HostMapConsumer consume{c->glow_host};
+    glow_finalize(c, num_chars, enc_layers, num_flow_blocks, num_block_layers);
+  });
+}
+
+int tts_glow_encode(tts_ctx* c, const int64_t* d_ids, const int32_t* h_lens, int B, int T_max, float length_scale,
+                    int32_t* h_ylens, void* stream) {
+  return ctx_call(
+      c, stream, [&] { TTS_CHECK(c && d_ids && h_lens && h_ylens, "null argument"); },
+      [&] { glow_encode(c, d_ids, h_lens, nullptr, B, T_max, length_scale, h_ylens); });
+}
+
+int tts_glow_encode_spk(tts_ctx* c, const int64_t* d_ids, const int32_t* h_lens, const int32_t* h_speaker_ids, int B,
+                        int T_max, float length_scale, int32_t* h_ylens, void* stream) {
+  return ctx_call(
+      c, stream, [&] { TTS_CHECK(c && d_ids && h_lens && h_ylens, "null argument"); },
+      [&] { glow_encode(c, d_ids, h_lens, h_speaker_ids, B, T_max, length_scale, h_ylens); });
+}
+
+int tts_glow_decode(tts_ctx* c, const float* d_noise, float noise_scale, int Ty, float* d_y, float* d_ymean,
+                    float* d_attn, float* d_logw, void* stream) {
+  return ctx_call(
+      c, stream, [&] { TTS_CHECK(c && d_y && d_ymean && d_attn && d_logw, "null argument"); },
+      [&] { glow_decode(c, d_noise, noise_scale, Ty, d_y, d_ymean, d_attn, d_logw); });
+}
+
+}  // extern "C"

@@ -1,0 +1,474 @@
+// MelGAN / MB-MelGAN: weight packing, the generator, output conv + PQMF synthesis, and the
+// tts_melgan_* entry points.
+#include "host.h"
+#include "split16.h"
+
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+
+using namespace ttsh;
+
+static void melgan_finalize(tts_ctx* c, int in_ch, int out_ch, int base, const int32_t* ups, int n_up, int nres,
+                     int use_pqmf) {
+  auto& G = c->mg;
+  const auto& m = c->mg_host;
+  G.ready = false;
+  TTS_CHECK(nres >= 1 && nres <= 4, "num_res_blocks must be in [1, 4] (dilation <= 27)");
+  G.in_ch = in_ch;
+  G.out_ch = out_ch;
+  G.base = base;
+  G.nres = nres;
+  G.pqmf = use_pqmf;
+  G.ups.assign(ups, ups + n_up);
+  G.convT.clear();
+  G.dconv.clear();
+  G.fused.clear();
+  G.convT.resize(n_up);
+  G.convTm.clear();
+  G.convTm.resize(n_up);
+  G.dconv.resize((size_t)n_up * nres);
+  G.fused.resize((size_t)n_up * nres);
+  G.rb_wd16.clear();
+  G.rb_wf16.clear();
+  G.rb_wd16.resize((size_t)n_up * nres);
+  G.rb_wf16.resize((size_t)n_up * nres);
+  G.rb_wd16p.clear();
+  G.rb_wd16p.resize((size_t)n_up * nres);
+  int pl3[8] = {3}, pl0[8] = {0};
+  {
+    auto w = wn_weight(m, "layers.1", {base, in_ch, 7});
+    pack_conv(G.conv_in, w, need(m, "layers.1.bias", {base}).d, in_ch, base, 7, 1, 1, pl3);
+  }
+  int idx = 2, C = base;
+  for (int i = 0; i < n_up; ++i) {
+    const int u = ups[i];
+    TTS_CHECK(u % 2 == 0 && u <= 8, "upsample factors must be even and <= 8");
+    const int cin = base >> i, cout = base >> (i + 1);
+    const int p = u / 2;
+    const std::string nm = "layers." + std::to_string(idx + 1);
+    auto wt = wn_weight(m, nm, {cin, cout, 2 * u});  // ConvTranspose1d weight (Cin, Cout, K)
+    std::vector<float> Wm((size_t)u * cout * cin * 2);
+    int pls[8] = {0};
+    for (int ph = 0; ph < u; ++ph) {
+      const int dmax = (ph + p) / u, dmin = dmax - 1;
+      pls[ph] = -dmin;
+      for (int co = 0; co < cout; ++co)
+        for (int ci = 0; ci < cin; ++ci)
+          for (int jj = 0; jj < 2; ++jj) {
+            const int delta = dmin + jj;
+            const int k = ph + p - delta * u;
+            Wm[(((size_t)ph * cout + co) * cin + ci) * 2 + jj] = wt[((size_t)ci * cout + co) * (2 * u) + k];
+          }
+    }
+    pack_conv(G.convT[i], Wm, need(m, nm + ".bias", {cout}).d, cin, cout, 2, 1, u, pls);
+    bool wm_in_range = true;
+    for (float v : Wm) wm_in_range &= std::fabs(v) < F16_RANGE;
+    // the merged GEMM has u * cout rows, so it is covered even where cout alone is not (full-band 64 -> 32)
+    if (wm_in_range && conv_x3_supported(cin, u * cout, 2, 1)) {
+      const auto& bias = need(m, nm + ".bias", {cout}).d;
+      std::vector<float> bm((size_t)u * cout);
+      for (size_t r = 0; r < bm.size(); ++r) bm[r] = bias[r / u];
+      pack_conv_x3_only(G.convTm[i], merge_convT_phases(Wm, u, cin, cout), bm, cin, u * cout, 2);
+    }
+    C = cout;
+    for (int bk = 0; bk < nres; ++bk) {
+      const int d = 1;
+      int dil = 1;
+      for (int q = 0; q < bk; ++q) dil *= 3;
+      (void)d;
+      const std::string bn = "layers." + std::to_string(idx + 2) + ".blocks." + std::to_string(bk);
+      auto wd = wn_weight(m, bn + ".2", {C, C, 3});
+      int pld[8] = {dil};
+      pack_conv(G.dconv[(size_t)i * nres + bk], wd, need(m, bn + ".2.bias", {C}).d, C, C, 3, dil, 1, pld);
+      auto w1 = wn_weight(m, bn + ".4", {C, C, 1});
+      const std::string sn = "layers." + std::to_string(idx + 2) + ".shortcuts." + std::to_string(bk);
+      auto ws = wn_weight(m, sn, {C, C, 1});
+      std::vector<float> Wf((size_t)C * 2 * C), bf(C);
+      const auto& b1 = need(m, bn + ".4.bias", {C}).d;
+      const auto& bs = need(m, sn + ".bias", {C}).d;
+      for (int co = 0; co < C; ++co) {
+        std::memcpy(&Wf[(size_t)co * 2 * C], &w1[(size_t)co * C], C * 4);
+        std::memcpy(&Wf[(size_t)co * 2 * C + C], &ws[(size_t)co * C], C * 4);
+        bf[co] = b1[co] + bs[co];
+      }
+      pack_conv(G.fused[(size_t)i * nres + bk], Wf, bf, 2 * C, C, 1, 1, 1, pl0);
+      if (resblock_x3_supported(C)) {
+        std::vector<uint16_t> wd16, wf16;
+        pack_resblock_x3(wd, Wf, C, wd16, wf16);
+        G.rb_wd16[(size_t)i * nres + bk].upload(wd16);
+        G.rb_wf16[(size_t)i * nres + bk].upload(wf16);
+        if (C % 32 == 16) {
+          pack_resblock_x3p(wd, C, wd16);
+          G.rb_wd16p[(size_t)i * nres + bk].upload(wd16);
+        }
+      }
+    }
+    idx += 3;
+  }
+  {
+    const std::string nm = "layers." + std::to_string(idx + 2);
+    auto w = wn_weight(m, nm, {out_ch, C, 7});
+    const auto& bo = need(m, nm + ".bias", {out_ch}).d;
+    pack_conv(G.conv_out, w, bo, C, out_ch, 7, 1, 1, pl3);
+    G.C_last = C;
+    if (out_ch == 4) {
+      std::vector<float> wo((size_t)C * 7 * 4);
+      for (int o = 0; o < 4; ++o)
+        for (int ci = 0; ci < C; ++ci)
+          for (int k = 0; k < 7; ++k) wo[((size_t)ci * 7 + k) * 4 + o] = w[((size_t)o * C + ci) * 7 + k];
+      G.out_w.upload(wo);
+      G.out_b.upload(bo);
+    } else if (out_ch == 1) {  // full-band: [c][k] for launch_out_conv1
+      G.out_w.upload(w);
+      G.out_b.upload(bo);
+    }
+  }
+  if (use_pqmf) {
+    const auto& g = need(m, "pqmf_layer.G", {}).d;
+    auto it = m.find("pqmf_layer.G");
+    TTS_CHECK(it->second.shape.size() == 3 && it->second.shape[1] == out_ch, "pqmf_layer.G shape");
+    G.taps = (int)it->second.shape[2] - 1;
+    G.G.upload(g);
+  }
+  HIP_OK(hipDeviceSynchronize());
+  G.ready = true;
+}
+
+// blocks 0-2 of a C = 48 ResidualStack as one kernel (TTS_STACK_FUSE=0: block by block, for A/B)
+static bool stack_fuse_on() {
+  static const bool on = [] {
+    const char* e = std::getenv("TTS_STACK_FUSE");
+    return !e || std::atoi(e) != 0;
+  }();
+  return on;
+}
+// the C = 96 stack in one launch: off by default since round 5 (TTS_STACK_FUSE96=1 turns it on).
+// Same-box A/B over 4 bench runs each (profiles/r05/v17_stack96_ab.txt): vocoder 2.958 ms fused
+// against 2.922 ms with blocks 0-2 as three resblock_x3 launches; the stack kernel's halo
+// recompute (up to 24 extra rows per 96-position tile) now costs more than the two HBM round trips
+// of x it saves at this width, while at C = 48 (with the fused ConvTranspose) fusing still wins
+static bool stack_fuse96_on() {
+  static const bool on = [] {
+    const char* e = std::getenv("TTS_STACK_FUSE96");
+    return e && std::atoi(e) != 0;
+  }();
+  return on;
+}
+// the last upsample's ConvTranspose inside the C = 48 stack kernel (resstack_x3.hip CTU = 2);
+// TTS_CT_FUSE=0 keeps the separate conv_x3 launch
+static bool ct_fuse_on() {
+  static const bool on = [] {
+    const char* e = std::getenv("TTS_CT_FUSE");
+    return !e || std::atoi(e) != 0;
+  }();
+  return on;
+}
+
+int ttsh::run_generator(tts_ctx* c, const float* mel, const int32_t* h_lens, int B, int M_max, int pad, float* out,
+                  hipStream_t s, GenTail* tail, const int64_t* mel_strides, bool dev_lens) {
+  auto& G = c->mg;
+  auto& W = c->mws;
+  TTS_CHECK(G.ready, "melgan weights not finalized");
+  TTS_CHECK(B >= 1, "B >= 1");
+  for (int b = 0; b < B && !dev_lens; ++b) {
+    TTS_CHECK(h_lens[b] >= 1 && h_lens[b] <= M_max, "mel lens out of range");
+    TTS_CHECK(h_lens[b] + 2 * pad >= 4, "ReflectionPad1d(3): mel frames + 2*padding must be >= 4");
+    for (int k = 0; k < G.nres && !G.ups.empty(); ++k)  // ResidualStack ReflectionPad1d(dilation), stage 0
+      TTS_CHECK((long)(h_lens[b] + 2 * pad) * G.ups[0] > G.dconv[k].dil,
+                "ReflectionPad1d: a residual stack's dilation must be < the first stage's length");
+  }
+  const int Lb = M_max + 2 * pad;
+  int up = 1;
+  for (int u : G.ups) up *= u;
+  size_t maxelems = (size_t)G.base * Lb;
+  {
+    int mul = 1, Cc = G.base;
+    for (int u : G.ups) {
+      mul *= u;
+      Cc /= 2;
+      maxelems = std::max(maxelems, (size_t)Cc * Lb * mul);
+    }
+  }
+  // device lengths: the ticket slot's (a fused submission's vocoder) or the workspace's
+  int* vld = c->vlens_override;
+  if (!vld) {
+    W.lens.ensure(B * 4);
+    vld = W.lens.i();
+  }
+  W.xa.ensure((size_t)B * maxelems * 4);
+  W.xb.ensure((size_t)B * maxelems * 4);
+  std::vector<int> lens(h_lens, h_lens + B);
+  if (!dev_lens) HIP_OK(hipMemcpyAsync(vld, lens.data(), B * 4, hipMemcpyHostToDevice, s));
+  else TTS_CHECK(c->vlens_override || W.lens.bytes >= (size_t)B * 4, "vocoder lengths buffer");
+  ConvCall cc;
+  cc.lens = vld;
+  cc.B = B;
+  cc.oflow = x3_flag(c);
+  cc.len_add = 2 * pad;
+  // layers[0..1]: replicate pad (inference_padding) + ReflectionPad1d(3) + Conv1d(k7)
+  if (mel_strides) {
+    TTS_CHECK(mel_strides[1] >= 1 && mel_strides[2] >= 1 && mel_strides[1] < (1L << 31) && mel_strides[2] < (1L << 31) &&
+                  (mel_strides[0] >= 1 || B == 1) && mel_strides[0] >= 0,
+              "mel strides must be positive");
+    TTS_CHECK(mel_strides[1] != 1 || (mel_strides[2] % 4 == 0 && (reinterpret_cast<uintptr_t>(mel) & 15) == 0),
+              "channel stride 1 needs a frame stride divisible by 4 and a 16-byte aligned mel");
+    cc.s[0] = src_of(mel, (long)mel_strides[0], (int)mel_strides[1], (int)mel_strides[2], G.in_ch, 0);
+  } else {
+    cc.s[0] = src_of(mel, (long)G.in_ch * M_max, M_max, 1, G.in_ch, 0);
+  }
+  cc.pad_mode = 1;
+  cc.rep_pad = pad;
+  cc.in_mul = cc.q_mul = 1;
+  cc.max_q = Lb;
+  float* x = W.xa.f();
+  float* xo = W.xb.f();
+  int C = G.base, mul = 1;
+  long Ls = Lb;
+  cc.out = x;
+  cc.ob = (long)C * Ls;
+  cc.oc = Ls;
+  cc.ot = 1;
+  run_conv(G.conv_in, cc, s);
+  cc.rep_pad = 0;
+  // blocks 0-2 of stage i as one resstack_x3 launch (x: the stage input; with ct, x is the
+  // ConvTranspose input and the kernel computes the stage input per tile): false if not covered
+  auto stack3 = [&](size_t i, int Cs, long Lss, int muls, const float* xs, float* ys, const ConvLayer* ct,
+                    const float* xin, int Cin, long Lin) {
+    if (!(cc.oflow && G.nres >= 3 && stack_fuse_on() && G.rb_wd16[i * G.nres].p)) return false;
+    if (Cs == 96 && !stack_fuse96_on()) return false;
+    int dil[3];
+    for (int k = 0; k < 3; ++k) dil[k] = G.dconv[i * G.nres + k].dil;
+    if (!resstack_x3_supported(Cs, dil, 3)) return false;
+    StackArgs sa{};
+    sa.B = B;
+    sa.x = xs;
+    sa.y = ys;
+    sa.sb = (long)Cs * Lss;
+    sa.Ls = (int)Lss;
+    sa.lens = vld;
+    sa.len_add = 2 * pad;
+    sa.mul = muls;
+    for (int k = 0; k < 3; ++k) {
+      sa.dil[k] = dil[k];
+      sa.wd16[k] = Cs % 32 == 16 ? G.rb_wd16p[i * G.nres + k].p : G.rb_wd16[i * G.nres + k].p;
+      sa.wf16[k] = G.rb_wf16[i * G.nres + k].p;
+      sa.bd[k] = G.dconv[i * G.nres + k].bias.f();
+      sa.bf[k] = G.fused[i * G.nres + k].bias.f();
+    }
+    sa.oflow = cc.oflow;
+    if (ct) {
+      sa.xin = xin;
+      sa.sb_in = (long)Cin * Lin;
+      sa.Ls_in = (int)Lin;
+      sa.ct16 = ct->W16.p;
+      sa.ct_bias = ct->bias.f();
+    }
+    if (!resstack_x3_fits(sa, lens.data())) return false;
+    launch_resstack_x3(sa, lens.data(), Cs, s);
+    return true;
+  };
+  for (size_t i = 0; i < G.ups.size(); ++i) {
+    const int u = G.ups[i];
+    int bk0 = 0;
+    if (u == 2 && C == 96 && ct_fuse_on() && cc.oflow && G.convTm[i].W16.p &&
+        stack3(i, C / 2, Ls * u, mul * u, nullptr, xo, &G.convTm[i], x, C, Ls)) {
+      // LeakyReLU + ConvTranspose1d + blocks 0-2 in one launch (resstack_x3.hip CTU = 2)
+      std::swap(x, xo);
+      C /= 2;
+      Ls *= u;
+      mul *= u;
+      bk0 = 3;
+    }
+    // LeakyReLU + ConvTranspose1d as u polyphase 2-tap convs
+    ConvCall t = cc;
+    t.s[0] = src_of(x, (long)C * Ls, Ls, 1, C, 1);
+    t.pad_mode = 0;
+    t.in_mul = t.q_mul = mul;
+    t.max_q = Lb * mul;
+    t.out_mul = u;
+    const int Cn = C / 2;
+    const long Ln = Ls * u;
+    t.out = xo;
+    t.ob = (long)Cn * Ln;
+    t.oc = Ln;
+    t.ot = 1;
+    if (bk0 == 0) {
+      if (t.oflow && G.convTm[i].W16.p) {  // all u phases as one GEMM over input positions 0 .. L
+        t.out_mul = 1;
+        t.max_q = Lb * mul + 1;
+        t.merged_u = u;
+        run_conv(G.convTm[i], t, s);
+      } else {
+        run_conv(G.convT[i], t, s);
+      }
+      std::swap(x, xo);
+      C = Cn;
+      Ls = Ln;
+      mul *= u;
+      // blocks 0-2 in one pass over the stage (resstack_x3.hip)
+      if (stack3(i, C, Ls, mul, x, xo, nullptr, nullptr, 0, 0)) {
+        std::swap(x, xo);
+        bk0 = 3;
+      }
+    }
+    for (int bk = bk0; bk < G.nres; ++bk) {  // fused ResidualStack blocks (resblock.hip)
+      const ConvLayer& dl = G.dconv[i * G.nres + bk];
+      const ConvLayer& fl = G.fused[i * G.nres + bk];
+      ResArgs ra{};
+      ra.x = x;
+      ra.y = xo;
+      ra.sb = (long)C * Ls;
+      ra.Ls = (int)Ls;
+      ra.lens = vld;
+      ra.len_add = 2 * pad;
+      ra.mul = mul;
+      ra.dil = dl.dil;
+      ra.Wd = dl.W.f();
+      ra.bd = dl.bias.f();
+      ra.Wf = fl.W.f();
+      ra.bf = fl.bias.f();
+      ra.max_q = Lb * mul;
+      ra.B = B;
+      const DevBuf& w16 = G.rb_wd16[i * G.nres + bk];
+      if (cc.oflow && w16.p) {
+        ra.Wd16 = w16.p;
+        ra.Wf16 = G.rb_wf16[i * G.nres + bk].p;
+        ra.oflow = cc.oflow;
+        launch_resblock_x3(ra, lens.data(), C, s);
+      } else {
+        launch_resblock(ra, C, s);
+      }
+      std::swap(x, xo);
+    }
+  }
+  if (tail) {
+    tail->x = x;
+    tail->C = C;
+    tail->Ls = Ls;
+    tail->mul = mul;
+    return up;
+  }
+  if (G.out_ch == 1) {  // full-band output stage on the VALU (melgan_out.hip)
+    HIP_OK(hipMemsetAsync(out, 0, (size_t)B * Ls * 4, s));
+    launch_out_conv1(x, (long)C * Ls, Ls, C, G.out_w.f(), G.out_b.f(), vld, 2 * pad, mul, (int)(Lb * mul), B,
+                     out, Ls, s);
+    return up;
+  }
+  ConvCall o = cc;
+  o.s[0] = src_of(x, (long)C * Ls, Ls, 1, C, 1);
+  o.pad_mode = 1;
+  o.in_mul = o.q_mul = mul;
+  o.max_q = Lb * mul;
+  o.epi = 2;
+  o.out = out;
+  o.ob = (long)G.out_ch * Ls;
+  o.oc = Ls;
+  o.ot = 1;
+  HIP_OK(hipMemsetAsync(out, 0, (size_t)B * G.out_ch * Ls * 4, s));
+  run_conv(G.conv_out, o, s);
+  return up;
+}
+
+void ttsh::mbmelgan_body(tts_ctx* c, const float* d_mel, const int64_t* mel_strides, const int32_t* h_lens, int B,
+                         int M_max, int pad, float* d_wav, bool dev_lens, hipStream_t s) {
+  if (!s) s = c->s;
+  auto& G = c->mg;
+  int up = 1;
+  for (int u : G.ups) up *= u;
+  const long Ls = (long)(M_max + 2 * pad) * up;
+  const bool fused = G.out_ch == 4 && G.taps == 62 && (G.C_last == 32 || G.C_last == 48);
+  if (fused) {  // launch_out_pqmf writes the rows' zero padding itself
+    GenTail t;
+    run_generator(c, d_mel, h_lens, B, M_max, pad, nullptr, s, &t, mel_strides, dev_lens);
+    TTS_CHECK(t.Ls == Ls, "generator length bookkeeping");
+    const int* dl = c->vlens_override ? c->vlens_override : c->mws.lens.i();
+    TTS_CHECK(launch_out_pqmf(t.x, (long)t.C * t.Ls, t.Ls, t.C, G.out_w.f(), G.out_b.f(), G.G.f(), G.out_ch,
+                              G.taps, dl, 2 * pad, up, (int)Ls, B, d_wav, (long)G.out_ch * Ls, s),
+              "fused output/PQMF shape not covered");
+  } else {
+    HIP_OK(hipMemsetAsync(d_wav, 0, (size_t)B * G.out_ch * Ls * 4, s));
+    c->mws.bands.ensure((size_t)B * G.out_ch * Ls * 4);
+    run_generator(c, d_mel, h_lens, B, M_max, pad, c->mws.bands.f(), s, nullptr, mel_strides, dev_lens);
+    const int* dl = c->vlens_override ? c->vlens_override : c->mws.lens.i();
+    launch_pqmf_synthesis(c->mws.bands.f(), (long)G.out_ch * Ls, Ls, G.G.f(), G.out_ch, G.taps, dl,
+                          2 * pad, up, (int)Ls, B, d_wav, (long)G.out_ch * Ls, s);
+  }
+}
+
+int ttsh::vocoder_min_len(const MelganModel& G, int pad) {
+  int L = std::max(1, 4 - 2 * pad);
+  for (int k = 0; k < G.nres && !G.ups.empty(); ++k)
+    while ((long)(L + 2 * pad) * G.ups[0] <= G.dconv[k].dil) ++L;
+  return L;
+}
+
+static int melgan_infer_impl(tts_ctx* c, const float* d_mel, const int64_t* mel_strides, const int32_t* h_lens, int B,
+                             int M_max, int pad, float* d_wav, void* stream) {
+  return ctx_call(
+      c, stream,
+      [&] {
+        TTS_CHECK(c && d_mel && h_lens && d_wav, "null argument");
+        TTS_CHECK(pad >= 0, "pad >= 0");
+        TTS_CHECK(c->mg.ready && c->mg.pqmf, "melgan (with PQMF) not finalized");
+      },
+      [&] { mbmelgan_body(c, d_mel, mel_strides, h_lens, B, M_max, pad, d_wav); });
+}
+
+extern "C" {
+
+int tts_melgan_set_tensor(tts_ctx* c, const char* name, const float* h, const int64_t* shape, int ndim) {
+  return stage_tensor(c, &tts_ctx::mg_host, name, h, shape, ndim);
+}
+
+int tts_melgan_finalize(tts_ctx* c, int in_ch, int out_ch, int base, const int32_t* ups, int n_up, int nres,
+                        int use_pqmf) {
+  return guarded_ctx(c, [&] {
+    TTS_CHECK(c && ups && n_up >= 1 && n_up <= 6, "bad arguments");
+    DeviceGuard g(c->device);
+    HIP_OK(hipStreamSynchronize(c->sv));  // no submitted vocoder still reads the weights replaced here
+    c->sv_live = false;
+    HostMapConsumer consume{c->mg_host};
+    melgan_finalize(c, in_ch, out_ch, base, ups, n_up, nres, use_pqmf);
+  });
+}
+
+int tts_melgan_generator(tts_ctx* c, const float* d_mel, const int32_t* h_lens, int B, int M_max, int pad,
+                         float* d_out, void* stream) {
+  return ctx_call(
+      c, stream,
+      [&] {
+        TTS_CHECK(c && d_mel && h_lens && d_out, "null argument");
+        TTS_CHECK(pad >= 0, "pad >= 0");
+      },
+      [&] { run_generator(c, d_mel, h_lens, B, M_max, pad, d_out, c->s); });
+}
+
+int tts_melgan_infer(tts_ctx* c, const float* d_mel, const int32_t* h_lens, int B, int M_max, int pad,
+                     float* d_wav, void* stream) {
+  return melgan_infer_impl(c, d_mel, nullptr, h_lens, B, M_max, pad, d_wav, stream);
+}
+
+int tts_melgan_infer_strided(tts_ctx* c, const float* d_mel, int64_t stride_b, int64_t stride_c, int64_t stride_t,
+                             const int32_t* h_lens, int B, int M_max, int pad, float* d_wav, void* stream) {
+  const int64_t st[3] = {stride_b, stride_c, stride_t};
+  return melgan_infer_impl(c, d_mel, st, h_lens, B, M_max, pad, d_wav, stream);
+}
+
+int tts_pqmf_synthesis(tts_ctx* c, const float* d_x, int B, int N, int L, const float* d_G, int taps, float* d_y,
+                       void* stream) {
+  return guarded_ctx(c, [&] {
+    TTS_CHECK(c && d_x && d_G && d_y, "null argument");
+    TTS_CHECK(B >= 1 && N >= 1 && N <= 8 && L >= 1 && taps >= 0, "bad sizes");
+    DeviceGuard g(c->device);
+    enter(c, stream);
+    std::vector<int> lens(B, L);
+    c->mws.lens.ensure(B * 4);
+    HIP_OK(hipMemcpyAsync(c->mws.lens.p, lens.data(), B * 4, hipMemcpyHostToDevice, c->s));
+    launch_pqmf_synthesis(d_x, (long)N * L, L, d_G, N, taps, c->mws.lens.i(), 0, 1, L, B, d_y, (long)N * L, c->s);
+    HIP_OK(hipStreamSynchronize(c->s));
+    leave(c, stream);
+  });
+}
+
+}  // extern "C"

@@ -1,0 +1,1001 @@
+// Tacotron2, running: the decoder step launches and their captured graphs, the encoder and
+// postnet, the persistent decoder, taco_infer, and the tts_taco_* inference entry points.
+#include "host.h"
+#include "decoder.h"
+#include "gsync.h"
+#include "split16.h"
+
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+using namespace ttsh;
+
+namespace {
+
+DecDev make_dev(tts_ctx* c, int Bact) {
+  auto& W = c->tws;
+  DecDev d{};
+  int* ci = W.ctl.i();
+  d.ctl = reinterpret_cast<DecCtl*>(ci);
+  d.done = ci + 4;
+  d.steps = ci + 4 + BMAX;
+  d.status = ci + 4 + 2 * BMAX;
+  d.max_steps = ci + 4 + 3 * BMAX;
+  d.lens = W.lens.i();
+  d.dec_out = W.dec.f();
+  d.align_out = W.align.f();
+  d.stop_out = W.stop.f();
+  d.S_cap = W.S_cap;
+  d.T_max = W.T_max;
+  d.B = Bact;
+  return d;
+}
+
+// columns [k0, k0 + K) of a fragment-order activation with Ktot columns
+SkSeg seg(const float* base, int Ktot, int k0, int K) {
+  SkSeg s;
+  s.ptr = base + (long)(k0 / 16) * 256;
+  s.ms = 16 * Ktot;
+  s.K = K;
+  return s;
+}
+
+SkJob job0() {
+  SkJob j;
+  std::memset(&j, 0, sizeof(j));
+  return j;
+}
+
+// the 5 launches of decoder step j of a chunk (parity j & 1 selects the h_dec buffer) over the
+// first MT batch tiles (rows >= 16*MT must all be finished)
+void enqueue_step(tts_ctx* c, int j, int which_only, hipStream_t s, int MT) {
+  auto& M = c->taco;
+  auto& W = c->tws;
+  const DecDev d = make_dev(c, std::min(W.B, 16 * MT));
+  const int r = W.r, YLD = 80 * M.r_init;
+  float* hd_cur = (j & 1) ? W.hdec1.f() : W.hdec0.f();
+  float* hd_nxt = (j & 1) ? W.hdec0.f() : W.hdec1.f();
+  if (which_only < 0 || which_only == 1) {  // K1: prenet layers 1+2 || stop(t-1)
+    SkArgs a{};
+    a.njobs = 2;
+    a.MT = MT;
+    SkJob& J = a.job[0] = job0();  // layer 1 (result kept in LDS)
+    J.seg[0] = seg(W.y.f(), YLD, 80 * (r - 1), 80);
+    J.nseg = 1;
+    J.K = 80;
+    J.W = M.pre1.f();
+    J.ntiles = 16;
+    SkJob& J2 = a.job[1] = job0();  // layer 2
+    J2.K = 256;
+    J2.W = M.pre2.f();
+    J2.ntiles = 16;
+    J2.out = W.pb.f();
+    J2.out_ld = 256;
+    J2.out_frag = 1;
+    StopArgs st{};
+    st.part = W.spart.f();
+    st.threshold = W.thr;
+    launch_prenet_stop(a, d, st, j, s);
+  }
+  if (which_only < 0 || which_only == 3) {  // K2: attention_rnn + partial query projection
+    SkArgs a{};
+    a.njobs = 1;
+    a.MT = MT;
+    SkJob& J = a.job[0] = job0();
+    J.seg[0] = seg(W.pb.f(), 256, 0, 256);
+    J.nseg = 1;
+    J.K = 256;
+    J.W = M.att_p.f();
+    J.ntiles = 256;
+    J.epi = EPI_LSTM;
+    J.addin = W.gatt.f();
+    J.addin_ld = 4096;
+    J.h_out = W.hatt.f();
+    J.c_state = W.catt.f();
+    J.hc_ld = 1024;
+    J.WqT = M.WqT.f();
+    J.pq_part = W.pq.f();
+    J.pq_cap = 128;
+    launch_skinny(a, d, j, 2, 4, s);  // 128 workgroups of 8 units: 128 query partials
+  }
+  if (which_only < 0 || which_only == 4) {  // K3: attention
+    AttnArgs p{};
+    p.pq_part = W.pq.f();
+    p.npq = 128;
+    p.Bp = MT * 16;
+    p.alpha = W.alpha.f();
+    p.alpha_cum = W.acum.f();
+    p.Wloc = M.Wloc.f();
+    p.WdT = M.Wdense.f();
+    p.v = M.v.f();
+    p.bv = M.bv;
+    p.penc = W.penc.f();
+    p.energy = W.energy.f();
+    p.enc = W.enc.f();
+    p.ctx = W.ctx.f();
+    p.part_s = W.aps.f();
+    p.part_m = W.apm.f();
+    p.part_u = W.apu.f();
+    p.counter = reinterpret_cast<unsigned*>(W.acnt.p);
+    p.nchmax = (W.T_max + 15) / 16;
+    p.softmax = M.softmax;
+    launch_attention(p, d, j, s);
+  }
+  if (which_only < 0 || which_only == 0) {  // K4: decoder_rnn LSTMCell
+    SkArgs a{};
+    a.njobs = 1;
+    a.MT = MT;
+    SkJob& J = a.job[0] = job0();
+    J.seg[0] = seg(W.hatt.f(), 1024, 0, 1024);
+    J.seg[1] = seg(W.ctx.f(), 512, 0, 512);
+    J.seg[2] = seg(hd_cur, 1024, 0, 1024);
+    J.nseg = 3;
+    J.K = 2560;
+    J.W = M.dec_w.f();
+    J.ntiles = 256;
+    J.epi = EPI_LSTM;
+    J.bias = M.dec_bias.f();
+    J.h_out = hd_nxt;
+    J.c_state = W.cdec.f();
+    J.hc_ld = 1024;
+    launch_skinny(a, d, j, 1, 4, s);
+  }
+  if (which_only < 0 || which_only == 5) {  // K5: projection + stop logit || next attention_rnn ctx/h part
+    SkArgs a{};
+    a.njobs = 2;
+    a.MT = MT;
+    SkJob& J = a.job[0] = job0();
+    J.seg[0] = seg(hd_nxt, 1024, 0, 1024);
+    J.seg[1] = seg(W.ctx.f(), 512, 0, 512);
+    J.nseg = 2;
+    J.K = 1536;
+    J.W = M.proj_w.f();
+    J.ntiles = 1 + 5 * r;  // stopnet tile + the first r frames (tacotron2.py:297)
+    J.epi = EPI_STORE;
+    J.bias = M.proj_b.f();
+    J.out = W.y.f();
+    J.out_ld = YLD;
+    J.out_frag = 1;
+    J.frames_r = r;
+    J.lead_stop = 1;
+    J.stop_part = W.spart.f();
+    SkJob& J2 = a.job[1] = job0();  // (+ biases)
+    J2.seg[0] = seg(W.ctx.f(), 512, 0, 512);
+    J2.seg[1] = seg(W.hatt.f(), 1024, 0, 1024);
+    J2.nseg = 2;
+    J2.K = 1536;
+    J2.W = M.att_pre.f();
+    J2.ntiles = 256;
+    J2.epi = EPI_STORE;
+    J2.bias = M.att_bias.f();
+    J2.out = W.gatt.f();
+    J2.out_ld = 4096;
+    launch_skinny(a, d, j, 1, 4, s);
+  }
+}
+
+__global__ void bcast_rows_kernel(const float* src, int n, float* dst, int rows) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n * rows; i += gridDim.x * blockDim.x)
+    dst[i] = src[i % n];
+}
+
+// Per-row biases of the persistent decoder, one column per thread:
+//   out[m][n] = base[n] + sum_e spk[m][e] WT[e][n]   (m < B; rows B..Bp-1 get base[n])
+// base = 0 on the attention_rnn / decoder_rnn / processed-inputs columns, the projection bias on
+// the projection columns [pj0, N). With no speaker (Es = 0) only the projection columns are built.
+constexpr int SPK_BMAX = 64;
+// Per-row speaker biases W_s s (+ the projection bias for the projection columns): out[m][n] for
+// rows m < Bp. Workgroup = 64 columns x 4 waves, wave q summing the speaker dims e = q, q + 4, ...
+// (the speaker values are wave-uniform scalar loads), the 4 partials added in a fixed order
+// through LDS. Round 4: the previous form (one column per thread over all dims, 64 accumulators
+// predicated on B) ran ~40 workgroups for ~400 us per call.
+template <int MB>
+__global__ __launch_bounds__(256) void spk_bias_kernel(const float* __restrict__ spk, int B, int Es,
+                                                       const float* __restrict__ WT, int N,
+                                                       const float* __restrict__ pjb, int pj0, int Bp,
+                                                       float* __restrict__ out) {
+  __shared__ float red[3][MB][64];
+  const int c = threadIdx.x & 63;
+  const int q = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int n = blockIdx.x * 64 + c;
+  const int nc = min(n, N - 1);
+  float acc[MB];
+#pragma unroll
+  for (int m = 0; m < MB; ++m) acc[m] = 0.f;
+  for (int e = q; e < Es; e += 4) {
+    const float w = WT[(long)e * N + nc];
+#pragma unroll
+    for (int m = 0; m < MB; ++m) {
+      const float sv = m < B ? spk[m * Es + e] : 0.f;  // wave-uniform
+      acc[m] = fmaf(sv, w, acc[m]);
+    }
+  }
+  if (q > 0) {
+#pragma unroll
+    for (int m = 0; m < MB; ++m) red[q - 1][m][c] = acc[m];
+  }
+  __syncthreads();
+  if (q != 0 || n >= N) return;
+  const float base = n >= pj0 ? pjb[n - pj0] : 0.f;
+#pragma unroll
+  for (int m = 0; m < MB; ++m)
+    if (m < Bp) out[(long)m * N + n] = base + (m < B ? ((acc[m] + red[0][m][c]) + red[1][m][c]) + red[2][m][c] : 0.f);
+  for (int m = MB; m < Bp; ++m) out[(long)m * N + n] = base;  // rows past the speaker rows (Bp > MB)
+}
+
+// rowmap (optional, device): encoder row b reads ids row rowmap[b] (the decode order)
+void run_encoder(tts_ctx* c, const int64_t* ids, int B, int T_max, float* enc_out, hipStream_t s,
+                 const int* rowmap = nullptr) {
+  auto& M = c->taco;
+  auto& W = c->tws;
+  const int* lens = W.lens.i();
+  launch_embed_gather(ids, T_max, M.emb.f(), M.num_chars, 512, lens, B, W.x0.f(), s, rowmap);
+  ConvCall cc;
+  cc.lens = lens;
+  cc.B = B;
+  cc.oflow = x3_flag(c);
+  cc.max_q = T_max;
+  cc.pad_mode = 0;
+  cc.epi = 1;
+  cc.s[0] = src_of(W.x0.f(), (long)T_max * 512, 1, 512, 512, 0);
+  cc.out = W.ca.f();
+  cc.ob = (long)512 * T_max;
+  cc.oc = T_max;
+  cc.ot = 1;
+  run_conv(M.enc[0], cc, s);
+  cc.s[0] = src_of(W.ca.f(), (long)512 * T_max, T_max, 1, 512, 0);
+  cc.out = W.cb.f();
+  run_conv(M.enc[1], cc, s);
+  cc.s[0] = src_of(W.cb.f(), (long)512 * T_max, T_max, 1, 512, 0);
+  cc.out = W.ca.f();
+  run_conv(M.enc[2], cc, s);
+  cc.s[0] = src_of(W.ca.f(), (long)512 * T_max, T_max, 1, 512, 0);
+  cc.out = W.gin.f();  // (B, T_max, 2048): time-major, so one step's gates of a tile are contiguous
+  cc.ob = (long)2048 * T_max;
+  cc.oc = 1;
+  cc.ot = 2048;
+  cc.epi = 0;
+  run_conv(M.lstm_in, cc, s);
+  // one cooperative launch for the whole recurrence (W.lc then holds its grid-barrier words; its
+  // fill zeroes enc_out too); per-step launches when cooperative launch is unavailable or
+  // TTS_ENCODER=steps
+  const char* e = std::getenv("TTS_ENCODER");
+  W.enc_ndom = (e && std::string(e) == "steps")
+                   ? 0
+                   : launch_bilstm_persist(W.gin.f(), M.whhT.f(), c->gemm_x3 ? M.whhT16.h() : nullptr, lens, T_max, B,
+                                           W.lh.f(), reinterpret_cast<unsigned*>(W.lc.p), enc_out, s);
+  W.enc_persist = W.enc_ndom > 0;
+  if (!W.enc_persist) {
+    HIP_OK(hipMemsetAsync(enc_out, 0, (size_t)B * T_max * 512 * 4, s));
+    launch_bilstm(W.gin.f(), M.whhT.f(), lens, T_max, B, W.lh.f(), W.lc.f(), enc_out, s);
+  }
+}
+
+// a persistent BiLSTM whose grid barrier timed out set its error word. The words are read on the
+// library stream (ordered after the BiLSTM launch and its arm fill; c->s is non-blocking, so a
+// null-stream copy would not be), then the stream is drained before they are looked at.
+void check_encoder_barrier(tts_ctx* c) {
+  if (!c->tws.enc_persist) return;
+  int* pw = c->pinned + 240;  // one error word per recurrence (2 directions x up to 2 row groups)
+  const int nd = std::min(c->tws.enc_ndom, ENC_NDOM_MAX);
+  pw[0] = pw[1] = pw[2] = pw[3] = 0;
+  const unsigned* words = reinterpret_cast<const unsigned*>(c->tws.lc.p);
+  for (int i = 0; i < nd; ++i) HIP_OK(hipMemcpyAsync(&pw[i], words + i * BAR_WORDS + 16, 4, hipMemcpyDeviceToHost, c->s));
+  HIP_OK(hipStreamSynchronize(c->s));
+  TTS_CHECK(pw[0] == 0 && pw[1] == 0 && pw[2] == 0 && pw[3] == 0, "persistent BiLSTM: grid barrier timed out (workgroups not co-resident) or preempted past TTS_BARRIER_TIMEOUT_MS; retrying the call is safe)");
+}
+
+void run_postnet(tts_ctx* c, const float* dec, long dec_b, const int* mlens, int B, int Mmax_alloc, int max_q,
+                 float* out, long out_b, hipStream_t s) {
+  auto& M = c->taco;
+  auto& W = c->tws;
+  ConvCall cc;
+  cc.lens = mlens;
+  cc.B = B;
+  cc.oflow = x3_flag(c);
+  cc.max_q = max_q;
+  cc.pad_mode = 0;
+  cc.epi = 2;
+  cc.s[0] = src_of(dec, dec_b, 1, 80, 80, 0);
+  cc.out = W.pa.f();
+  cc.ob = (long)512 * Mmax_alloc;
+  cc.oc = Mmax_alloc;
+  cc.ot = 1;
+  run_conv(M.post[0], cc, s);
+  float* bufs[2] = {W.pa.f(), W.pbb.f()};
+  for (int i = 1; i < 4; ++i) {
+    cc.s[0] = src_of(bufs[(i - 1) & 1], (long)512 * Mmax_alloc, Mmax_alloc, 1, 512, 0);
+    cc.out = bufs[i & 1];
+    run_conv(M.post[i], cc, s);
+  }
+  cc.s[0] = src_of(bufs[1], (long)512 * Mmax_alloc, Mmax_alloc, 1, 512, 0);
+  cc.out = out;
+  cc.ob = out_b;
+  cc.oc = 1;
+  cc.ot = 80;
+  cc.epi = 0;
+  cc.resid = dec;
+  cc.rb = dec_b;
+  cc.rc = 1;
+  cc.rt = 80;
+  run_conv(M.post[4], cc, s);
+}
+
+template <class T>
+__global__ void gather_rows_kernel(const T* __restrict__ src, T* __restrict__ dst, const int* __restrict__ map,
+                                   long row) {
+  const long i = blockIdx.y;
+  const T* sr = src + (long)map[i] * row;
+  T* dr = dst + i * row;
+  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < row; e += (long)gridDim.x * blockDim.x) dr[e] = sr[e];
+}
+
+// dst row i <- src row map[i], i < B
+template <class T>
+void gather_rows(const T* src, T* dst, const int* d_map, long row, int B, hipStream_t s) {
+  if (row <= 0 || B <= 0) return;
+  dim3 g((unsigned)std::min<long>((row + 255) / 256, 64), B);
+  gather_rows_kernel<T><<<g, 256, 0, s>>>(src, dst, d_map, row);
+  HIP_OK(hipGetLastError());
+}
+
+// the decoder's four outputs scattered back to the caller's row order in one launch (entry z)
+struct Gather4 {
+  const float* src[4];
+  float* dst[4];
+  long row[4];
+};
+__global__ void gather4_rows_kernel(Gather4 g, const int* __restrict__ map) {
+  const int z = blockIdx.z;
+  const long row = g.row[z], i = blockIdx.y;
+  const float* __restrict__ sr = g.src[z] + (long)map[i] * row;
+  float* __restrict__ dr = g.dst[z] + i * row;
+  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < row; e += (long)gridDim.x * blockDim.x) dr[e] = sr[e];
+}
+void gather4_rows(const Gather4& g, const int* d_map, int B, hipStream_t s) {
+  long mx = 0;
+  for (int z = 0; z < 4; ++z) mx = std::max(mx, g.row[z]);
+  if (mx <= 0 || B <= 0) return;
+  gather4_rows_kernel<<<dim3((unsigned)std::min<long>((mx + 255) / 256, 64), B, 4), 256, 0, s>>>(g, d_map);
+  HIP_OK(hipGetLastError());
+}
+
+// Per-call host arguments as kernel arguments (one launch instead of three pageable uploads):
+// decode order and its inverse, lengths in decode order, and the decoder control block
+// [base, all_done, active_tiles, pad | done | steps | status | max_steps] (DecCtl + BMAX each)
+struct TacoSetup {
+  int B, MT;
+  int perm[BMAX], inv[BMAX], lens[BMAX], max_steps[BMAX];
+};
+__global__ void taco_setup_kernel(TacoSetup a, int* map, int* lens, int* ctl, unsigned* zero_flag) {
+  if (zero_flag && threadIdx.x == 0) *zero_flag = 0u;  // a fused call's range flag (no separate fill)
+  for (int e = threadIdx.x; e < 4 + 4 * BMAX; e += blockDim.x) {
+    const int ms = e - 4 - 3 * BMAX;
+    ctl[e] = e == 2 ? a.MT : (ms >= 0 && ms < a.B ? a.max_steps[ms] : 0);
+  }
+  const int i = threadIdx.x;
+  if (i < a.B) {
+    map[i] = a.perm[i];
+    map[BMAX + i] = a.inv[i];
+    lens[i] = a.lens[i];
+  }
+}
+
+// element (m, k) of a fragment-order activation; ps: published pre-split (decoder_persist.hip
+// stc_quad_x3: the f16 hi / lo halves of k & ~3 .. + 3 as [hi 4 | lo 4] in their 16 bytes), read back
+// as hi + 2^-11 lo, the value the decoder's split-f16 GEMMs consumed
+__device__ __forceinline__ float frag_value(const float* p, int m, int k, int K, int ps) {
+  if (!ps) return p[frag_idx(m, k, K)];
+  const _Float16* q = reinterpret_cast<const _Float16*>(p + frag_idx(m, k & ~3, K));
+  return (float)q[k & 3] + (float)q[4 + (k & 3)] * SPLIT_INV;
+}
+
+// decoder state in the caller's row order (tts_taco_decoder_state): fragment-order activations
+// (h_att, h_dec, ctx) and row-major cells / attention rows of decode row inv[b] -> row b
+__global__ void taco_state_kernel(const float* hatt, const float* catt, const float* hdec, const float* cdec,
+                                  const float* ctx, const float* alpha, const float* acum, const int* inv, int T_max,
+                                  int ps, float* o_ha, float* o_ca, float* o_hd, float* o_cd, float* o_ctx,
+                                  float* o_al, float* o_ac) {
+  const int b = blockIdx.y, m = inv[b];
+  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < 1024; k += gridDim.x * blockDim.x) {
+    if (o_ha) o_ha[(long)b * 1024 + k] = frag_value(hatt, m, k, 1024, ps);
+    if (o_ca) o_ca[(long)b * 1024 + k] = catt[(long)m * 1024 + k];
+    if (o_hd) o_hd[(long)b * 1024 + k] = frag_value(hdec, m, k, 1024, ps);
+    if (o_cd) o_cd[(long)b * 1024 + k] = cdec[(long)m * 1024 + k];
+    if (o_ctx && k < 512) o_ctx[(long)b * 512 + k] = frag_value(ctx, m, k, 512, ps);
+  }
+  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < T_max; k += gridDim.x * blockDim.x) {
+    if (o_al) o_al[(long)b * T_max + k] = alpha[(long)m * T_max + k];
+    if (o_ac) o_ac[(long)b * T_max + k] = acum[(long)m * T_max + k];
+  }
+}
+
+// decode-order mel lengths for the postnet (steps * r), from the decoder results on the device
+__global__ void taco_mlens_kernel(const int* ctl, int B, int r, int* mlens) {
+  const int i = threadIdx.x;
+  if (i < B) mlens[i] = ctl[4 + BMAX + i] * r;
+}
+
+// gather every status word the host checks after a Tacotron2 call into one block (TS_* layout)
+struct DecSlots {
+  int v[PMAX_LAUNCH];
+};
+// A fused call (vlens set) also writes the vocoder's mel lengths in caller order, steps * r of
+// decode row inv[b], raised to Lmin where shorter (TS_VERR: the call fails)
+__global__ void taco_status_kernel(const unsigned* enc_bar, int nenc, const unsigned* dec_bar, DecSlots dslot, int ndec,
+                                   const int* ctl, const unsigned* flag, int* st, int B, const int* inv, int r,
+                                   int Lmin, int* vlens) {
+  const int i = threadIdx.x;
+  int short_row = 0;
+  if (vlens && i < B) {
+    int L = ctl[4 + BMAX + inv[i]] * r;
+    if (L < Lmin) {
+      short_row = 1;
+      L = Lmin;
+    }
+    vlens[i] = L;
+  }
+  short_row = __syncthreads_or(short_row);
+  if (i == 0) st[TS_VERR] = short_row;
+  if (i < 3 * BMAX) st[TS_RES + i] = ctl[4 + i];
+  if (i < ENC_NDOM_MAX) st[TS_ENC + i] = enc_bar && i < nenc ? (int)enc_bar[i * BAR_WORDS + 16] : 0;
+  if (i < PMAX_LAUNCH) {
+    st[TS_DEC + i] = dec_bar && i < ndec ? (int)dec_bar[dslot.v[i] * BAR_WORDS + 16] : 0;
+  }
+  if (i == 0) st[TS_FLAG] = flag ? (int)*flag : 0;
+}
+
+// CHUNK-step graph for batch tile count MT (captured once per configuration)
+hipGraphExec_t step_graph(tts_ctx* c, int MT, hipStream_t s) {
+  auto& W = c->tws;
+  if (W.graphs[MT]) return W.graphs[MT];
+  hipGraph_t g;
+  HIP_OK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+  try {
+    for (int j = 0; j < CHUNK; ++j) enqueue_step(c, j, -1, s, MT);
+    launch_dec_advance(reinterpret_cast<DecCtl*>(W.ctl.p), CHUNK, s);
+  } catch (...) {
+    hipGraph_t tmp;
+    (void)hipStreamEndCapture(s, &tmp);
+    throw;
+  }
+  HIP_OK(hipStreamEndCapture(s, &g));
+  HIP_OK(hipGraphInstantiate(&W.graphs[MT], g, nullptr, nullptr, 0));
+  HIP_OK(hipGraphDestroy(g));
+  return W.graphs[MT];
+}
+
+bool use_persistent(tts_ctx* c) {
+  const char* e = std::getenv("TTS_DECODER");
+  if (e && std::string(e) == "graph") return false;
+  return c->tws.MT <= PMAX_LAUNCH && persist_supported(c->device);
+}
+
+// the whole decode as one cooperative launch per batch-tile count (decoder_persist.hip)
+void run_persistent(tts_ctx* c, int r, float thr, hipStream_t s) {
+  auto& M = c->taco;
+  auto& W = c->tws;
+  build_pj(c, r);
+  PArgs a{};
+  a.dec_w = M.dec_w.f();
+  a.dec_b = M.dec_bias.f();
+  a.apre_w = M.att_pre.f();
+  a.apre_b = M.att_bias.f();
+  a.attp_w = M.att_p.f();
+  a.x3flag = x3_flag(c);  // null in fp32 mode
+  // split-f16 decoder GEMM parts: only with every split weight set in range, and Q = 1024,
+  // E = 512, prenet 256 (the kernel's fixed geometry, checked by build_pj's callers)
+  const bool dx3 = a.x3flag && M.att_p_x3.p && M.dec_x3.p && M.apre_x3.p && M.pj_x3.p && !std::getenv("TTS_DECODER_F32");
+  a.attp_x3 = dx3 ? M.att_p_x3.h() : nullptr;
+  a.dec_x3 = dx3 ? M.dec_x3.h() : nullptr;
+  a.apre_x3 = dx3 ? M.apre_x3.h() : nullptr;
+  a.pj_x3 = dx3 ? M.pj_x3.h() : nullptr;
+  a.pj_w = M.pj_w.f();
+  a.pj_b = M.pj_b.f();
+  {  // per-row biases: projection (always), speaker columns when the model has them
+    const int YP = (1 + 5 * r + 16) * 16;
+    const int N = M.spk_dim ? 8320 + YP : YP;
+    const int pj0 = M.spk_dim ? 8320 : 0;
+    const int Bp = W.MT * 16;
+    grow<float>(W.spkb, (size_t)64 * (8320 + 112 * 16), W.gen);
+    TTS_CHECK(W.B <= SPK_BMAX || !M.spk_dim, "multi-speaker decoding: at most 64 utterances per call");
+    const int Bs = M.spk_dim ? W.B : 0;
+    TTS_CHECK(M.spk_dim <= 512, "speaker vectors of at most 512 dims");
+    // Graves with speakers: the projection columns hold W_s s alone; the kernel adds the bias and
+    // scales W_s s by the step's sum of attention weights (PArgs::spk_scale)
+    a.spk_scale = M.graves && M.spk_dim ? 1 : 0;
+    {
+      const float* wt = M.spk_dim ? M.spk_wT.f() : nullptr;
+      const int es = M.spk_dim, p0 = a.spk_scale ? N : pj0;
+      const dim3 g((N + 63) / 64);
+      if (Bs <= 16) spk_bias_kernel<16><<<g, 256, 0, s>>>(W.spk.f(), Bs, es, wt, N, M.pj_b.f(), p0, Bp, W.spkb.f());
+      else if (Bs <= 32) spk_bias_kernel<32><<<g, 256, 0, s>>>(W.spk.f(), Bs, es, wt, N, M.pj_b.f(), p0, Bp, W.spkb.f());
+      else spk_bias_kernel<64><<<g, 256, 0, s>>>(W.spk.f(), Bs, es, wt, N, M.pj_b.f(), p0, Bp, W.spkb.f());
+    }
+    HIP_OK(hipGetLastError());
+    a.spk_ld = N;
+    a.pjb_rows = W.spkb.f() + pj0;
+    a.spk_att = M.spk_dim ? W.spkb.f() : nullptr;
+    a.spk_dec = M.spk_dim ? W.spkb.f() + 4096 : nullptr;
+    a.spk_penc = M.spk_dim ? W.spkb.f() + 8192 : nullptr;
+  }
+  // decoder variants
+  a.pre1_b0 = M.prenet_bn ? M.pre1_b0.f() : nullptr;
+  a.pre2_b = M.prenet_bn ? M.pre2_b.f() : nullptr;
+  a.win = M.windowing;
+  a.fwd = M.forward_attn;
+  a.trans = M.forward_attn && M.trans_agent;
+  a.fwd_mask = M.forward_attn && M.forward_attn_mask;
+  a.ta_w = M.trans_agent ? M.ta_w.f() : nullptr;
+  a.ta_b = M.ta_b;
+  a.win_idx = W.win_idx.i();
+  a.fwd_u = W.fwd_u.f();
+  a.part_f = W.apf.f();
+  if (M.windowing) HIP_OK(hipMemsetAsync(W.win_idx.p, 0xff, 64 * 4, s));  // -1: before the first step
+  a.gK = M.graves ? M.graves_K : 0;
+  a.na1_w = M.na1_w.f();
+  a.na1_b = M.na1_b.f();
+  a.na2_w = M.na2_w.f();
+  a.na2_b = M.na2_b.f();
+  a.gh = W.gh.f();
+  a.gmu = W.gmu.f();
+  if (M.graves) HIP_OK(hipMemsetAsync(W.gmu.p, 0, 64 * 16 * 4, s));  // mu_prev = 0 (common_layers.py:143)
+  if (M.forward_attn) {
+    static const std::vector<float> half(64, 0.5f);  // u = 0.5 (common_layers.py:241)
+    HIP_OK(hipMemcpyAsync(W.fwd_u.p, half.data(), 64 * 4, hipMemcpyHostToDevice, s));
+  }
+  a.pre2_w = M.pre2.f();
+  a.WqT = M.WqT.f();
+  a.Wcomb = M.Wcomb.f();
+  a.v = M.v.f();
+  a.bv = M.bv;
+  a.nt_proj = 1 + 5 * r;
+  a.ntj = a.nt_proj + 16;
+  a.r = r;
+  a.penc = W.penc.f();
+  a.enc = W.enc.f();
+  a.ypart = W.ypart.f();
+  a.pb = W.pb.f();
+  a.gatt = W.gatt.f();
+  a.hatt = W.hatt.f();
+  a.catt = W.catt.f();
+  a.hdec0 = W.hdec0.f();
+  a.hdec1 = W.hdec1.f();
+  a.cdec = W.cdec.f();
+  a.ctx = W.ctx.f();
+  a.pq = W.pq.f();
+  a.alpha = W.alpha.f();
+  a.acum = W.acum.f();
+  a.energy = W.energy.f();
+  a.part_s = W.aps.f();
+  a.part_m = W.apm.f();
+  a.part_u = W.apu.f();
+  a.counter = reinterpret_cast<unsigned*>(W.acnt.p);
+  a.nchmax = (W.T_max + persist_attn_tc() - 1) / persist_attn_tc();
+  a.anorm = W.anorm.f();
+  a.defer_align = persist_defer_ok(W.B * a.nchmax) && !std::getenv("TTS_ALIGN_IN_P4");
+  a.softmax = M.softmax;
+  a.thr = thr;
+  a.bar = reinterpret_cast<unsigned*>(W.pbar.p);
+  // TTS_PTRACE=<file>: phase timestamps of 8 steps from step TTS_PTRACE_T0 (default 100)
+  DevBuf& trace_buf = W.trace;
+  const char* tr = std::getenv("TTS_PTRACE");
+  TTS_CHECK(!tr || persist_trace_built(), "TTS_PTRACE needs a library built with -DTTS_PHASE_TRACE "
+                                          "(tools/build_variants.sh trace -DTTS_PHASE_TRACE; TTSHIP_LIB=tools/var/lib_trace.so)");
+  if (tr) {
+    trace_buf.ensure((size_t)8 * 24 * 256 * 8);
+    HIP_OK(hipMemsetAsync(trace_buf.p, 0, (size_t)8 * 24 * 256 * 8, s));
+    a.trace = static_cast<unsigned long long*>(trace_buf.p);
+    a.atrace = a.trace + (size_t)8 * 16 * 256;
+    const char* t0 = std::getenv("TTS_PTRACE_T0");
+    a.trace_t0 = t0 ? std::atoi(t0) : 100;
+  }
+  // TTS_PTRACE_LAUNCH: which launch of the MT cascade is traced (default 0, the first)
+  const int trace_li = [] {
+    const char* e = std::getenv("TTS_PTRACE_LAUNCH");
+    return e ? std::atoi(e) : 0;
+  }();
+  unsigned long long* const trace_p = a.trace;
+  unsigned long long* const atrace_p = a.atrace;
+  static const bool xdiag = std::getenv("TTS_DIAG_XCC") != nullptr;
+  DevBuf& xdiag_buf = W.xdiag;
+  if (xdiag) xdiag_buf.ensure((size_t)PMAX_LAUNCH * 256 * 4);
+  c->dec_nlaunch = 0;
+  c->dec_presplit = persist_presplit(a);
+  for (int mt = W.MT; mt >= 1; --mt) {
+    const int li = W.MT - mt;  // launch index: its barrier block (armed in taco_infer's state fill)
+    a.bar = reinterpret_cast<unsigned*>(W.pbar.p) + BAR_WORDS * W.pslot[li];
+    a.base_out = W.stat.i() + TS_END + li;
+    a.D = make_dev(c, std::min(W.B, 16 * mt));
+    a.trace = li == trace_li ? trace_p : nullptr;
+    a.atrace = li == trace_li ? atrace_p : nullptr;
+    a.diag = xdiag ? static_cast<unsigned*>(xdiag_buf.p) + 256 * li : nullptr;
+    // launch timing from the dispatches themselves: ev_dec[0] at the first launch's start, ev_dec[i + 1]
+    // at launch i's end (event-record packets between the launches cost ~5 us of idle each)
+    launch_persist_decoder(a, mt, s, false, li == 0 ? c->ev_dec[0] : nullptr, c->ev_dec[li + 1]);
+    if (tr && li == trace_li) {  // one launch is traced
+      HIP_OK(hipStreamSynchronize(s));
+      std::vector<unsigned long long> h((size_t)8 * 24 * 256);
+      HIP_OK(hipMemcpy(h.data(), trace_buf.p, h.size() * 8, hipMemcpyDeviceToHost));
+      if (FILE* fp = std::fopen(tr, "wb")) {
+        std::fwrite(h.data(), 8, h.size(), fp);
+        std::fclose(fp);
+      }
+      a.trace = nullptr;
+      a.atrace = nullptr;
+      tr = nullptr;
+    }
+    c->dec_nlaunch++;
+  }
+  a.diag = nullptr;
+  if (xdiag) {  // TTS_DIAG_XCC: print each launch's workgroup -> XCD map and the hand-off addresses
+    HIP_OK(hipStreamSynchronize(s));
+    std::vector<unsigned> h((size_t)PMAX_LAUNCH * 256);
+    HIP_OK(hipMemcpy(h.data(), xdiag_buf.p, h.size() * 4, hipMemcpyDeviceToHost));
+    for (int li = 0; li < c->dec_nlaunch; ++li) {
+      std::fprintf(stderr, "TTS_DIAG_XCC launch %d: wg0 xcc %u, wg0..15:", li, h[li * 256]);
+      for (int k = 0; k < 16; ++k) std::fprintf(stderr, " %u", h[li * 256 + k]);
+      std::fprintf(stderr, "\n");
+    }
+    std::fprintf(stderr, "TTS_DIAG_XCC addresses: bar %p pq %p hatt %p ctx %p hdec0 %p pb %p\n", (void*)W.pbar.p,
+                 (void*)a.pq, (void*)a.hatt, (void*)a.ctx, (void*)a.hdec0, (void*)a.pb);
+  }
+}
+
+}  // namespace
+
+void ttsh::taco_infer(tts_ctx* c, const int64_t* ids, const int32_t* h_lens, int B, int T_max, int r,
+                const int32_t* h_max_steps, int S_cap, float thr, float* d_dec, float* d_post, float* d_align,
+                float* d_stop, int32_t* h_steps, int32_t* h_status, void* stream,
+                const int64_t* d_spk_ids, const float* d_spk_emb, const FusedVoc* fv) {
+  auto& M = c->taco;
+  TTS_CHECK(M.ready, "tacotron2 weights not finalized");
+  TTS_CHECK(B >= 1 && B <= BMAX, "B must be in [1, 64]");
+  TTS_CHECK(T_max >= 1 && T_max <= 4096, "T_max must be in [1, 4096]");
+  TTS_CHECK(r >= 1 && r <= M.r_init, "r must be in [1, r_init]");
+  int max_ms = 0;
+  for (int b = 0; b < B; ++b) {
+    TTS_CHECK(h_lens[b] >= 1 && h_lens[b] <= T_max, "lens out of range");
+    TTS_CHECK(h_max_steps[b] >= 1, "max_decoder_steps must be >= 1");
+    max_ms = std::max(max_ms, (int)h_max_steps[b]);
+  }
+  TTS_CHECK(S_cap >= max_ms, "S_cap < max(max_steps)");
+  taco_workspace(c, B, T_max, S_cap, r);
+  auto& W = c->tws;
+  hipStream_t s = c->s;
+  enter(c, stream);
+  // Decode order: longest expected first (max_decoder_steps, then text length), so the rows still
+  // decoding at the end sit in the first batch tiles and the step can shrink to fewer tiles.
+  // Every row is independent, so the order changes nothing but speed; outputs are scattered back.
+  std::vector<int> perm(B), inv(B);
+  for (int b = 0; b < B; ++b) perm[b] = b;
+  std::stable_sort(perm.begin(), perm.end(), [&](int x, int y) {
+    if (h_max_steps[x] != h_max_steps[y]) return h_max_steps[x] > h_max_steps[y];
+    return h_lens[x] > h_lens[y];
+  });
+  for (int i = 0; i < B; ++i) inv[perm[i]] = i;
+  // decode order, its inverse, lengths and the control block (base = 0, all_done = 0,
+  // active_tiles = MT, done/steps/status = 0, max_steps) in one launch, as kernel arguments
+  {
+    TacoSetup ta{};
+    ta.B = B;
+    ta.MT = W.MT;
+    for (int i = 0; i < B; ++i) {
+      ta.perm[i] = perm[i];
+      ta.inv[i] = inv[i];
+      ta.lens[i] = h_lens[perm[i]];
+      ta.max_steps[i] = h_max_steps[perm[i]];
+    }
+    taco_setup_kernel<<<1, 256, 0, s>>>(ta, W.map.i(), W.lens.i(), W.ctl.i(), fv ? x3_flag(c) : nullptr);
+    HIP_OK(hipGetLastError());
+  }
+  int* d_map = W.map.i();
+  W.thr = thr;
+  // speaker vectors in decode order: external embeddings, or rows of the learned table
+  TTS_CHECK(!M.variant() || use_persistent(c), "BN prenet / attention windowing / forward / Graves attention run on "
+                                               "the persistent decoder only (<= 64 utterances per call on a 256-CU "
+                                               "device)");
+  if (M.spk_dim) {
+    TTS_CHECK(d_spk_ids || d_spk_emb, "multi-speaker model: speaker ids or speaker embeddings are required");
+    TTS_CHECK(use_persistent(c), "multi-speaker decoding runs on the persistent decoder only (<= 64 utterances "
+                                 "per call on a 256-CU device)");
+    if (d_spk_emb) {
+      gather_rows<float>(d_spk_emb, W.spk.f(), d_map, M.spk_dim, B, s);
+    } else {
+      TTS_CHECK(M.num_spk > 0, "model has no speaker_embedding table: pass speaker embeddings");
+      gather_rows<int64_t>(d_spk_ids, reinterpret_cast<int64_t*>(W.spkid.p), d_map, 1, B, s);
+      launch_embed_gather(reinterpret_cast<const int64_t*>(W.spkid.p), 1, M.spk_table.f(), M.num_spk, M.spk_dim,
+                          W.lens.i(), B, W.spk.f(), s);
+    }
+  }
+  // encoder + processed inputs
+  run_encoder(c, ids, B, T_max, W.enc.f(), s, d_map);
+  {
+    ConvCall cc;
+    cc.lens = W.lens.i();
+    cc.B = B;
+    cc.oflow = x3_flag(c);
+    cc.max_q = T_max;
+    cc.s[0] = src_of(W.enc.f(), (long)T_max * 512, 1, 512, 512, 0);
+    cc.out = W.penc.f();
+    cc.ob = (long)T_max * 128;
+    cc.oc = 1;
+    cc.ot = 128;
+    run_conv(M.penc, cc, s);
+  }
+  // decoder state
+  const int Bp = W.MT * 16;
+  const bool persist = use_persistent(c);
+  if (persist && !W.pslot_cal) {  // ordered after the caller's work (enter above) and this call's encoder
+    pick_barrier_blocks(reinterpret_cast<unsigned*>(W.pbar.p), PBAR_CAND, PMAX_LAUNCH, W.pslot, s);
+    W.pslot_cal = true;
+  }
+  {
+    FillList f;  // decoder state and outputs zeroed in one launch (the postnet output too)
+    f.add(W.catt.p, (size_t)Bp * 1024 * 4);
+    f.add(W.hatt.p, (size_t)Bp * 1024 * 4);
+    f.add(W.hdec0.p, (size_t)Bp * 1024 * 4);
+    f.add(W.hdec1.p, (size_t)Bp * 1024 * 4);
+    f.add(W.cdec.p, (size_t)Bp * 1024 * 4);
+    f.add(W.ctx.p, (size_t)Bp * 512 * 4);
+    f.add(W.y.p, (size_t)Bp * 80 * M.r_init * 4);
+    f.add(W.alpha.p, (size_t)B * T_max * 4);
+    f.add(W.acum.p, (size_t)B * T_max * 4);
+    f.add(W.dec.p, (size_t)B * S_cap * r * 80 * 4);
+    f.add(W.align.p, (size_t)B * S_cap * T_max * 4);
+    f.add(W.stop.p, (size_t)B * S_cap * 4);
+    f.add(W.acnt.p, BMAX * sizeof(unsigned));
+    f.add(W.post.p, (size_t)B * S_cap * r * 80 * 4);
+    if (persist)
+      for (int li = 0; li < W.MT; ++li) add_barrier_fills(f, reinterpret_cast<unsigned*>(W.pbar.p) + BAR_WORDS * W.pslot[li], 1);
+    launch_fills(f, s);
+  }
+  bcast_rows_kernel<<<256, 256, 0, s>>>(M.att_bias.f(), 4096, W.gatt.f(), Bp);
+  HIP_OK(hipGetLastError());
+  c->dec_path = persist ? 1 : 0;
+  if (persist) {
+    run_persistent(c, r, thr, s);
+  } else {
+  // step graphs, cached per configuration / buffer generation
+  if (W.graph_gen != W.gen || W.gB != B || W.gT != T_max || W.gS != S_cap || W.gr != r || W.gthr != thr) {
+    for (auto& ge : W.graphs)
+      if (ge) {
+        HIP_OK(hipGraphExecDestroy(ge));
+        ge = nullptr;
+      }
+    W.graph_gen = W.gen;
+    W.gB = B;
+    W.gT = T_max;
+    W.gS = S_cap;
+    W.gr = r;
+    W.gthr = thr;
+  }
+  for (int mt = 1; mt <= W.MT; ++mt) step_graph(c, mt, s);
+  // run chunks until every utterance is done (checked one chunk behind) or t > max steps; drop
+  // to fewer batch tiles once the trailing rows have all finished
+  const int chunks_max = max_ms / CHUNK + 1;  // covers t = max_ms (stop of the last step)
+  bool done = false;
+  int mt = W.MT;
+  for (int ch = 0; ch < chunks_max && !done; ++ch) {
+    HIP_OK(hipGraphLaunch(W.graphs[mt], s));
+    HIP_OK(hipMemcpyAsync(&c->pinned[2 * (ch & 1)], &reinterpret_cast<DecCtl*>(W.ctl.p)->all_done, 8,
+                          hipMemcpyDeviceToHost, s));
+    HIP_OK(hipEventRecord(c->ev_chunk[ch & 1], s));
+    if (ch >= 1) {
+      HIP_OK(hipEventSynchronize(c->ev_chunk[(ch - 1) & 1]));
+      const int* pv = &c->pinned[2 * ((ch - 1) & 1)];
+      if (pv[0]) done = true;
+      else if (pv[1] >= 1 && pv[1] < mt) mt = pv[1];
+    }
+  }
+  }
+  // postnet over each row's own frames: lengths from the decoder results on the device, grid sized
+  // by S_cap (tiles past a row's length exit at entry), so the decode needs no host round trip
+  taco_mlens_kernel<<<1, 64, 0, s>>>(W.ctl.i(), B, r, W.mlens.i());
+  HIP_OK(hipGetLastError());
+  const long fb = (long)S_cap * r * 80;  // W.post was zeroed with the decoder state
+  run_postnet(c, W.dec.f(), fb, W.mlens.i(), B, S_cap * r, S_cap * r, W.post.f(), fb, s);
+  // scatter back to the caller's row order: output row b <- decode row inv[b]
+  gather4_rows(Gather4{{W.post.f(), W.dec.f(), W.align.f(), W.stop.f()}, {d_post, d_dec, d_align, d_stop},
+                       {fb, fb, (long)S_cap * T_max, (long)S_cap}},
+               d_map + BMAX, B, s);
+  // one host round trip per call: barrier error words, per-row results, range flag, launch steps
+  {
+    const unsigned* lc = reinterpret_cast<const unsigned*>(W.lc.p);
+    taco_status_kernel<<<1, 256, 0, s>>>(W.enc_persist ? lc : nullptr, W.enc_ndom,
+                                         persist ? reinterpret_cast<const unsigned*>(W.pbar.p) : nullptr,
+                                         DecSlots{{W.pslot[0], W.pslot[1], W.pslot[2], W.pslot[3]}}, c->dec_nlaunch, W.ctl.i(), c->gemm_x3 ? x3_flag(c) : nullptr, W.stat.i(),
+                                         B, d_map + BMAX, r, fv ? fv->Lmin : 0, fv ? fv->vlens : nullptr);
+    HIP_OK(hipGetLastError());
+    int* pin = c->pinned;
+    HIP_OK(hipMemcpyAsync(pin + TS_ENC, W.stat.i() + TS_ENC, (TS_N - TS_ENC) * 4, hipMemcpyDeviceToHost, s));
+    if (fv) {  // the vocoder goes in behind the status words; the host waits for the words only
+      HIP_OK(hipEventRecord(c->ev_status, s));
+      fv->enqueue();
+      HIP_OK(hipEventSynchronize(c->ev_status));
+    } else {
+      HIP_OK(hipStreamSynchronize(s));
+    }
+    TTS_CHECK(!W.enc_persist || (pin[TS_ENC] == 0 && pin[TS_ENC + 1] == 0 && pin[TS_ENC + 2] == 0 && pin[TS_ENC + 3] == 0),
+              "persistent BiLSTM: grid barrier timed out (workgroups not co-resident) or preempted past "
+              "TTS_BARRIER_TIMEOUT_MS; retrying the call is safe)");
+    TTS_CHECK(!persist || (pin[TS_DEC] == 0 && pin[TS_DEC + 1] == 0 && pin[TS_DEC + 2] == 0 && pin[TS_DEC + 3] == 0),
+              "persistent decoder: grid barrier timed out (workgroups not co-resident) or preempted past "
+              "TTS_BARRIER_TIMEOUT_MS; retrying the call is safe)");
+    if (c->gemm_x3) {  // with_x3_fallback reads the flag from here
+      pin[12] = pin[TS_FLAG];
+      c->flag_read = true;
+    }
+    for (int i = 0; i < PMAX_LAUNCH; ++i) c->dec_end[i] = persist && i < c->dec_nlaunch ? pin[TS_END + i] : 0;
+    TTS_CHECK(!fv || pin[TS_VERR] == 0, VOC_SHORT_MSG);
+  }
+  const int* res = c->pinned + TS_RES;
+  for (int i = 0; i < B; ++i) {
+    TTS_CHECK(res[i] == 1, "decoder did not finish an utterance (internal error)");
+    const int b = perm[i];
+    h_steps[b] = res[BMAX + i];
+    h_status[b] = res[2 * BMAX + i];
+  }
+  if (fv)  // the caller's stream waits for the decode's outputs here, for the vocoder at finish
+    HIP_OK(hipStreamWaitEvent((hipStream_t)stream, c->ev_status, 0));
+  else
+    leave(c, stream);
+  c->last_B = B;
+  c->last_T = T_max;
+  c->last_S = S_cap;
+  c->last_r = r;
+}
+
+extern "C" {
+
+int tts_taco_infer(tts_ctx* c, const int64_t* d_ids, const int32_t* h_lens, int B, int T_max, int r,
+                   const int32_t* h_max_steps, int S_cap, float thr, float* d_dec, float* d_post, float* d_align,
+                   float* d_stop, int32_t* h_steps, int32_t* h_status, void* stream) {
+  return tts_taco_infer_spk(c, d_ids, h_lens, B, T_max, r, h_max_steps, S_cap, thr, nullptr, nullptr, d_dec, d_post,
+                            d_align, d_stop, h_steps, h_status, stream);
+}
+
+int tts_taco_infer_spk(tts_ctx* c, const int64_t* d_ids, const int32_t* h_lens, int B, int T_max, int r,
+                       const int32_t* h_max_steps, int S_cap, float thr, const int64_t* d_spk_ids,
+                       const float* d_spk_emb, float* d_dec, float* d_post, float* d_align, float* d_stop,
+                       int32_t* h_steps, int32_t* h_status, void* stream) {
+  return guarded_ctx(c, [&] {
+    TTS_CHECK(c && d_ids && h_lens && h_max_steps && d_dec && d_post && d_align && d_stop && h_steps && h_status,
+              "null argument");
+    DeviceGuard g(c->device);
+    with_x3_fallback(c, [&] {
+      taco_infer(c, d_ids, h_lens, B, T_max, r, h_max_steps, S_cap, thr, d_dec, d_post, d_align, d_stop, h_steps,
+                 h_status, stream, d_spk_ids, d_spk_emb);
+    });
+  });
+}
+
+int tts_taco_encoder(tts_ctx* c, const int64_t* d_ids, const int32_t* h_lens, int B, int T_max, float* d_out,
+                     void* stream) {
+  return guarded_ctx(c, [&] {
+    TTS_CHECK(c && d_ids && h_lens && d_out, "null argument");
+    TTS_CHECK(c->taco.ready, "tacotron2 weights not finalized");
+    TTS_CHECK(B >= 1 && B <= BMAX && T_max >= 1, "bad sizes");
+    for (int b = 0; b < B; ++b) TTS_CHECK(h_lens[b] >= 1 && h_lens[b] <= T_max, "lens out of range");
+    DeviceGuard g(c->device);
+    taco_workspace(c, B, T_max, std::max(1, c->tws.S_cap), std::max(1, c->tws.r));
+    enter(c, stream);
+    std::vector<int> lens(h_lens, h_lens + B);
+    HIP_OK(hipMemcpyAsync(c->tws.lens.p, lens.data(), B * 4, hipMemcpyHostToDevice, c->s));
+    with_x3_fallback(c, [&] { run_encoder(c, d_ids, B, T_max, d_out, c->s); });
+    check_encoder_barrier(c);
+    leave(c, stream);
+  });
+}
+
+int tts_taco_postnet(tts_ctx* c, const float* d_dec, const int32_t* h_lens, int B, int M_max, float* d_out,
+                     void* stream) {
+  return guarded_ctx(c, [&] {
+    TTS_CHECK(c && d_dec && h_lens && d_out, "null argument");
+    TTS_CHECK(c->taco.ready, "tacotron2 weights not finalized");
+    TTS_CHECK(B >= 1 && B <= BMAX && M_max >= 1, "bad sizes");
+    DeviceGuard g(c->device);
+    auto& W = c->tws;
+    long gen = W.gen;
+    grow<int>(W.mlens, BMAX, gen);
+    grow<float>(W.pa, (size_t)B * 512 * M_max, gen);
+    grow<float>(W.pbb, (size_t)B * 512 * M_max, gen);
+    W.gen = gen;
+    int maxM = 0;
+    for (int b = 0; b < B; ++b) {
+      TTS_CHECK(h_lens[b] >= 1 && h_lens[b] <= M_max, "lens out of range");
+      maxM = std::max(maxM, (int)h_lens[b]);
+    }
+    enter(c, stream);
+    std::vector<int> lens(h_lens, h_lens + B);
+    HIP_OK(hipMemcpyAsync(W.mlens.p, lens.data(), B * 4, hipMemcpyHostToDevice, c->s));
+    HIP_OK(hipMemsetAsync(d_out, 0, (size_t)B * M_max * 80 * 4, c->s));
+    with_x3_fallback(c, [&] {
+      run_postnet(c, d_dec, (long)M_max * 80, W.mlens.i(), B, M_max, maxM, d_out, (long)M_max * 80, c->s);
+    });
+    HIP_OK(hipStreamSynchronize(c->s));
+    leave(c, stream);
+  });
+}
+
+int tts_taco_decoder_state(tts_ctx* c, int B, int T_max, float* d_att_h, float* d_att_c, float* d_dec_h,
+                           float* d_dec_c, float* d_context, float* d_alpha, float* d_alpha_cum, void* stream) {
+  return guarded_ctx(c, [&] {
+    TTS_CHECK(c->last_B > 0, "run tts_taco_infer first");
+    TTS_CHECK(B == c->last_B && T_max == c->last_T,
+              "decoder state: the buffers' (B, T_max) differ from the last decode on this context");
+    TTS_CHECK(c->dec_path == 1 && c->dec_nlaunch >= 1, "decoder state: the last decode did not run the persistent "
+                                                       "decoder (TTS_DECODER=graph or a non-256-CU device)");
+    DeviceGuard g(c->device);
+    auto& W = c->tws;
+    // the last executed step t_end - 1 wrote h_dec into hdec[(t_end - 1) & 1 ? 0 : 1]
+    // (decoder_persist.hip P5: hd_nxt = (t & 1) ? hdec0 : hdec1)
+    const int t_end = c->dec_end[c->dec_nlaunch - 1];
+    TTS_CHECK(t_end >= 1, "decoder state: no decoder step ran");
+    const float* hdec = ((t_end - 1) & 1) ? W.hdec0.f() : W.hdec1.f();
+    enter(c, stream);
+    taco_state_kernel<<<dim3(4, c->last_B), 256, 0, c->s>>>(W.hatt.f(), W.catt.f(), hdec, W.cdec.f(), W.ctx.f(),
+                                                            W.alpha.f(), W.acum.f(), W.map.i() + BMAX, c->last_T,
+                                                            c->dec_presplit ? 1 : 0, d_att_h, d_att_c, d_dec_h, d_dec_c, d_context, d_alpha,
+                                                            d_alpha_cum);
+    HIP_OK(hipGetLastError());
+    leave(c, stream);
+  });
+}
+
+int tts_decoder_stats(tts_ctx* c, int* path, int* nlaunch, float* ms, int* steps) {
+  return guarded_ctx(c, [&] {
+    TTS_CHECK(c && path && nlaunch && ms && steps, "bad arguments");
+    TTS_CHECK(c->last_B > 0, "run tts_taco_infer first");
+    *path = c->dec_path;
+    *nlaunch = c->dec_path ? c->dec_nlaunch : 0;
+    int prev = 0;
+    for (int i = 0; i < *nlaunch; ++i) {
+      HIP_OK(hipEventElapsedTime(&ms[i], c->ev_dec[i], c->ev_dec[i + 1]));
+      steps[i] = c->dec_end[i] - prev;
+      prev = c->dec_end[i];
+    }
+  });
+}
+
+int tts_time_decoder_kernel(tts_ctx* c, int which, int iters, float* ms_out) {
+  return guarded_ctx(c, [&] {
+    TTS_CHECK(c && ms_out && iters >= 1, "bad arguments");
+    TTS_CHECK(c->last_B > 0 && c->tws.graphs[c->tws.MT], "run tts_taco_infer first");
+    TTS_CHECK(c->tws.S_cap >= CHUNK + 2, "S_cap too small for timing");
+    DeviceGuard g(c->device);
+    auto& W = c->tws;
+    hipStream_t s = c->s;
+    // live state of the last decode, re-armed: base = 1, nothing done, unbounded max steps
+    std::vector<int> ctl(4 + 4 * BMAX, 0);
+    ctl[0] = 1;
+    for (int b = 0; b < BMAX; ++b) ctl[4 + 3 * BMAX + b] = 1 << 30;
+    hipEvent_t e0, e1;
+    HIP_OK(hipEventCreate(&e0));
+    HIP_OK(hipEventCreate(&e1));
+    HIP_OK(hipMemcpyAsync(W.ctl.p, ctl.data(), ctl.size() * 4, hipMemcpyHostToDevice, s));
+    if (which == 0) enqueue_step(c, 0, 0, s, W.MT);  // warm-up
+    else HIP_OK(hipGraphLaunch(W.graphs[W.MT], s));
+    HIP_OK(hipMemcpyAsync(W.ctl.p, ctl.data(), ctl.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_OK(hipEventRecord(e0, s));
+    for (int i = 0; i < iters; ++i) {
+      if (which == 0) enqueue_step(c, 0, 0, s, W.MT);
+      else {
+        HIP_OK(hipGraphLaunch(W.graphs[W.MT], s));
+      }
+    }
+    HIP_OK(hipEventRecord(e1, s));
+    HIP_OK(hipEventSynchronize(e1));
+    float ms = 0.f;
+    HIP_OK(hipEventElapsedTime(&ms, e0, e1));
+    *ms_out = which == 0 ? ms / iters : ms / (iters * CHUNK);
+    // leave the control block in a finished state
+    ctl[1] = 1;
+    HIP_OK(hipMemcpy(W.ctl.p, ctl.data(), ctl.size() * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipEventDestroy(e0));
+    HIP_OK(hipEventDestroy(e1));
+  });
+}
+
+}  // extern "C"

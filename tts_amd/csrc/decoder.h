@@ -1,4 +1,4 @@
-// Decoder-step data structures shared by decoder.hip and api.hip.
+// Decoder-step data structures shared by decoder.hip and api_taco.hip.
 #pragma once
 #include "common.h"
 
@@ -116,7 +116,7 @@ struct PArgs {
   const uint16_t* pj_x3;    // pj_w split-f16 [ntj tiles][48][64][16] (with attp_x3)
   const float* pj_w;    // [ntj][96][64][4] stop tile, 5r frame tiles, 16 folded prenet-1 tiles
   const float* pj_b;    // [ntj * 16]
-  // per-row biases (api.hip spk_bias_kernel), row stride spk_ld: projection bias per row (always),
+  // per-row biases (api_taco.hip spk_bias_kernel), row stride spk_ld: projection bias per row (always),
   // speaker parts W_s s of the attention_rnn / decoder_rnn gates and processed inputs (null
   // without speakers)
   const float* pjb_rows;

@@ -1052,7 +1052,7 @@ __global__ __launch_bounds__(PT) void persist_decoder_kernel(PArgs P) {
 #pragma unroll
   for (int c = 0; c < NCK; ++c)
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {  // + the row's speaker part (W_dec,s s, api.hip spk_bias_kernel)
+    for (int q = 0; q < 4; ++q) {  // + the row's speaker part (W_dec,s s, api_taco.hip spk_bias_kernel)
       db[c][q] = P.dec_b[g * 16 + q * 4 + (tid & 3)];
       if (P.spk_dec && !(GRAVES && P.spk_scale))  // scaled per step below otherwise
         db[c][q] += P.spk_dec[(long)min(c * CB + (tid >> 2), Bp - 1) * P.spk_ld + g * 16 + q * 4 + (tid & 3)];

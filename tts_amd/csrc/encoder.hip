@@ -8,6 +8,7 @@
 #include "common.h"
 #include "decoder.h"  // frag_idx
 #include "gsync.h"
+#include "launch.h"
 #include "split16.h"
 
 // row stride of the LDS gate-partial reductions [wave][row][LRS]: writers put rows r and r + 4 of a

@@ -7,6 +7,7 @@
 //   positions t < length are written: the convolutions (conv.hip) read positions >= length as zero
 //   padding, which is what the reference's masks produce.
 #include "common.h"
+#include "launch.h"
 
 // LayerNorm over the channel dim (normalization.py:4-27, eps 1e-4). A workgroup owns 64 time
 // positions (one per lane, coalesced rows) x 4 channel groups (one per wave); the column's values

@@ -1,0 +1,55 @@
+// Launchers and host packers of the kernel files that have no header of their own (encoder.hip,
+// glow.hip, pwgan.hip). Each is declared here only; the file that defines it includes this header,
+// so the compiler checks the signature against the definition.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include <vector>
+
+// encoder.hip
+void launch_embed_gather(const int64_t* ids, int T_max, const float* table, int num_rows, int D,
+                         const int* lens, int B, float* out, hipStream_t s, const int* rowmap = nullptr);
+int launch_bilstm_persist(const float* Gin, const float* Whh, const uint16_t* Whh16, const int* lens, int T_max,
+                          int B, float* hbuf, unsigned* bar, float* out, hipStream_t s);
+bool launch_ge2e_pipe(const uint16_t* const* w16, const float* const* bias, int nl, const float* gin0, const int* lens,
+                      int T_max, int B, float* hbuf, unsigned* bar, float* out, hipStream_t s);
+bool launch_lstm768_persist(const float* Gin, const float* Whh, const uint16_t* Whh16, const int* lens, int T_max,
+                            int B, float* hbuf, unsigned* bar, float* out, hipStream_t s);
+void launch_bilstm(const float* Gin, const float* Whh, const int* lens, int T_max, int B, float* hbuf, float* cbuf,
+                   float* out, hipStream_t s);
+
+// glow.hip
+void launch_glu_ln_res(const float* x, long xb, int C2, const float* gamma, const float* beta, const float* res,
+                       long rb, float* out, long ob, const int* lens, int B, int T, hipStream_t s);
+void launch_ln(float* x, long xb, int C, const float* gamma, const float* beta, const int* lens, int B, int T,
+               hipStream_t s, bool relu = false);
+void launch_glow_mha(const float* qkv, int H, int heads, int T, const int* lens, float* out, int B, hipStream_t s);
+void launch_tds_depthwise(const float* x, int C, int T, const float* w, const float* bias, const int* lens, float* y,
+                          int B, hipStream_t s);
+void launch_glow_durations(const float* logw, int T, const int* lens, float length_scale, float* cum, int* ylen,
+                           float* wceil, int B, hipStream_t s);
+void launch_glow_expand(const float* o_mean, int C, int Tx, const int* xlens, const float* cum, const int* ylens,
+                        int Ty, const float* noise, float noise_scale, float* y_mean, float* z, float* attn, int B,
+                        hipStream_t s);
+void launch_glow_squeeze(const float* x, int C, int T, const int* ylens, float* y, int K, int B, hipStream_t s);
+void launch_glow_unsqueeze(const float* x, int C2, int K, const int* ylens, float* y, int T, int B, hipStream_t s);
+void launch_glow_speaker(const int* spk, const float* table, int c_in, int c_pad, float* g, int B, hipStream_t s);
+void launch_glow_embed(const int64_t* ids, int T, const float* table, int rows, int D, const int* lens, float* out,
+                       int B, hipStream_t s);
+
+// pwgan.hip
+void launch_pw_upsample(const float* in, long ib, int Lin_max, const int* lens, int len_add, int in_mul, int s,
+                        const float* h, float* out, long ob, int Lout_max, int C, int B, hipStream_t st);
+void launch_pw_first(const float* noise, long nb, const float* w, const float* bias, const int* lens, int len_add,
+                     int hop, float* x, int Tmax, int B, hipStream_t st);
+void launch_pw_layer(const float* x, const float* c, float* xn, float* skip, const float* W1, const float* b1,
+                     const float* W2, const float* b2, const int* lens, const float* zeros, int len_add, int hop,
+                     int Tmax, int dil, int first, int B, int variant, hipStream_t st);
+void launch_pw_layer_x3(const float* x, const float* c, float* xn, float* skip, const void* W1x, const float* b1,
+                        const void* W2x, const float* b2, const int* lens, const int* h_lens, int len_add, int hop,
+                        int Tmax, int dil, int first, int B, unsigned* oflow, hipStream_t st);
+void pack_pw_layer_x3(const std::vector<float>& m1, const std::vector<float>& m2, std::vector<uint16_t>& w1x,
+                      std::vector<uint16_t>& w2x);
+void launch_pw_out(const float* skip, float scale, const float* W3, const float* b3, const float* w4,
+                   const float* b4, const int* lens, int len_add, int hop, int Tmax, float* out, int B,
+                   hipStream_t st);

@@ -13,6 +13,7 @@
 //   epilogue  x' = (out + b + x) / 4  -> ping-pong buffer;  skip (+)= s + b  (in place)
 // HBM per sample per block: x (+halo, L2) 256 B, c 320 B, skip r/w 512 B, x' 256 B.
 #include "common.h"
+#include "launch.h"
 
 #include <cstdlib>
 #include "split16.h"
