@@ -27,6 +27,8 @@
  *                                    postnet output (TTS/server/synthesizer.py:150-159), one call
  *   tts_taco_mbmelgan_submit/finish <- the same, returning once the decode's results are on the host
  *                                    (the vocoder still running), completed by finish
+ *   tts_mel_to_linear / tts_griffin_lim <- AudioProcessor.inv_melspectrogram on a batch
+ *                                    (TTS/utils/audio.py:213-214, 241-248, 259-279)
  *
  * Conventions: every function returns 0 on success and nonzero on failure; the message is
  * available from tts_last_error() (thread-local). Pointers prefixed d_ are device (HIP) memory
@@ -210,6 +212,43 @@ int tts_ge2e_finalize(tts_ctx* ctx, int input_dim, int proj_dim, int lstm_dim, i
                       int use_lstm_with_projection);
 int tts_ge2e_infer(tts_ctx* ctx, const float* d_x, const int32_t* h_lens, int B, int T_max, float* d_out,
                    void* stream);
+
+/* ---- Griffin-Lim waveform stage (TTS/utils/audio.py, the path of a Synthesizer without a vocoder) ----
+   Both entries only enqueue kernels: no host synchronisation in either GEMM mode, no graph capture.
+
+   tts_mel_to_linear <- AudioProcessor._denormalize + _db_to_amp + _mel_to_linear and the power of
+                       inv_melspectrogram (audio.py:213-214, 241-248, 126-163):
+                       S = max(1e-10, inv_basis @ 10^((clip(mel) * scale + offset) / spec_gain)) ^ power
+   d_mel       (B, M_max, n_mels) normalised mel, frame-major (a Tacotron2 postnet output); row b is
+               read for t < h_lens[b] only (0 <= h_lens[b] <= M_max)
+   d_inv_basis (n_freq, n_mels) pseudo-inverse of the mel filterbank
+   d_scale, d_offset (n_mels) the denormalisation as dB = x * scale + offset per channel: covers the
+               mean-var scaler (std, mean) and the range normalisations (one value repeated);
+               use_clip != 0 clips x to [clip_lo, clip_hi] first (clip_norm)
+   d_S         (B, M_max, n_freq); frames t >= h_lens[b] are written as zero
+   1 <= B <= 64, 1 <= n_mels <= 512. */
+int tts_mel_to_linear(tts_ctx* ctx, const float* d_mel, const int32_t* h_lens, int B, int M_max, int n_mels,
+                      int n_freq, const float* d_inv_basis, const float* d_scale, const float* d_offset,
+                      float clip_lo, float clip_hi, int use_clip, float spec_gain, float power, float* d_S,
+                      void* stream);
+
+/* tts_griffin_lim <- AudioProcessor._griffin_lim (audio.py:259-279) on a batch: librosa.istft of
+                       S e^{2 pi i u}, then `iters` rounds of librosa.stft -> unit phase (a bin that is
+                       exactly 0 counts as phase 0) -> librosa.istft. Periodic Hann window of win_length
+                       points centred in n_fft, centred frames with reflect padding, window-square
+                       envelope division where the envelope exceeds 1e-11; fp32.
+   d_S         (B, M_max, n_fft / 2 + 1) target magnitudes, frame-major (tts_mel_to_linear's output)
+   d_phase0    (B, M_max, n_fft / 2 + 1) uniform [0, 1) numbers u, the initial phase / (2 pi)
+   d_wav       (B, hop_length * (M_max - 1)); row b holds hop_length * (h_lens[b] - 1) samples, the rest
+               of the row is written as zero. Frames t >= h_lens[b] of d_S / d_phase0 are never read.
+   Supported: n_fft == 1024, 1 <= win_length <= 1024, 64 <= hop_length <= 512, iters >= 0, 1 <= B <= 64,
+   and every row hop_length * (h_lens[b] - 1) > n_fft / 2 (the reflect padding's own requirement,
+   as torch.stft). Anything else is an error and launches nothing. Row b equals its own B = 1
+   call bit for bit. The frame buffers live in the context's workspace; the window and twiddle
+   tables are computed in double on the host once per win_length (a change of win_length waits for
+   the context's queued work before the upload). */
+int tts_griffin_lim(tts_ctx* ctx, const float* d_S, const int32_t* h_lens, int B, int M_max, int n_fft,
+                    int win_length, int hop_length, int iters, const float* d_phase0, float* d_wav, void* stream);
 
 /* Measurement hook for bench.py: average device time (ms) of `iters` launches of one kernel of the
    last tts_taco_infer configuration, timed with hipEvents on the context's stream.

@@ -81,6 +81,11 @@ SIGNATURES = [
     ("tts_set_gemm_mode", ctypes.c_int, [_vp, ctypes.c_int]),
     ("tts_test_stall_lstm", ctypes.c_int, [ctypes.c_int]),
     ("tts_gemm_mode", ctypes.c_int, [_vp, _c_i_p, _c_i64_p]),
+    ("tts_mel_to_linear", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                         _vp, _vp, _vp, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_float,
+                                         ctypes.c_float, _vp, _vp]),
+    ("tts_griffin_lim", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
 ]
 
 
@@ -337,6 +342,24 @@ class Engine:
         B, N, L = x.shape
         taps = G.shape[-1] - 1
         _check(self.lib.tts_pqmf_synthesis(self.h, _ptr(x), B, N, L, _ptr(G), taps, _ptr(y), _stream(x.device)))
+
+    def mel_to_linear(self, mel, lens, inv_basis, scale, offset, clip, spec_gain, power, S):
+        """Normalised mel (B, M, n_mels) -> linear magnitudes ``S`` (B, M, n_freq) (tts_mel_to_linear);
+        ``clip`` is None or the (lo, hi) bounds applied to the mel before denormalising."""
+        B, M, n_mels = mel.shape
+        lens_a, lens_p = _i32(lens)
+        lo, hi = (0.0, 0.0) if clip is None else clip
+        _check(self.lib.tts_mel_to_linear(self.h, _ptr(mel), lens_p, B, M, n_mels, S.shape[-1], _ptr(inv_basis),
+                                          _ptr(scale), _ptr(offset), float(lo), float(hi), int(clip is not None),
+                                          float(spec_gain), float(power), _ptr(S), _stream(mel.device)))
+
+    def griffin_lim(self, S, lens, n_fft, win_length, hop_length, iters, phase0, wav):
+        """Batched Griffin-Lim (tts_griffin_lim): magnitudes ``S`` and uniform [0, 1) ``phase0``
+        (B, M, n_fft / 2 + 1) -> ``wav`` (B, hop_length * (M - 1))."""
+        B, M, _ = S.shape
+        lens_a, lens_p = _i32(lens)
+        _check(self.lib.tts_griffin_lim(self.h, _ptr(S), lens_p, B, M, int(n_fft), int(win_length), int(hop_length),
+                                        int(iters), _ptr(phase0), _ptr(wav), _stream(S.device)))
 
     def decoder_stats(self):
         """(path, [(ms, steps) per persistent launch]) of the last Tacotron2 decode."""

@@ -4,7 +4,9 @@ is not in this image: the mel filterbank is librosa.filters.mel's published Slan
 STFT/ISTFT are torch.stft/istft with librosa's conventions (periodic Hann, centred frames, the
 config's pad mode), trimming is librosa.effects.trim's frame-RMS rule. Mean-var scaling (`stats_path`,
 audio.py:80-86,108-186) reads compute_statistics.py's stats file through a restricted loader
-(`load_stats_file`). None of these touch the GPU: the GPU path is the MB-MelGAN vocoder. Parity of the restated librosa pieces is unpinned
+(`load_stats_file`). By default none of these touch the GPU; the audio-config key
+``griffin_lim_device: "gpu"`` moves `inv_melspectrogram` onto the library's batched Griffin-Lim
+kernels (`inv_melspectrogram_batch`, fp32), everything else stays on the host. Parity of the restated librosa pieces is unpinned
 (librosa is not importable here to make fixtures); tests check their defining properties.
 """
 import io
@@ -134,7 +136,13 @@ class AudioProcessor:
                  frame_length_ms=None, hop_length=None, win_length=None, ref_level_db=None, fft_size=1024,
                  power=None, preemphasis=0.0, signal_norm=None, symmetric_norm=None, max_norm=None,
                  mel_fmin=None, mel_fmax=None, spec_gain=20, stft_pad_mode="reflect", clip_norm=True,
-                 griffin_lim_iters=None, do_trim_silence=False, trim_db=60, stats_path=None, **_):
+                 griffin_lim_iters=None, do_trim_silence=False, trim_db=60, stats_path=None, griffin_lim_device=None,
+                 **_):
+        if griffin_lim_device not in (None, "cpu", "gpu"):
+            raise ValueError(f"griffin_lim_device must be 'cpu' or 'gpu', got {griffin_lim_device!r}")
+        # None / "cpu": Griffin-Lim on the host (float64); "gpu": the library's batched kernels (fp32)
+        self.griffin_lim_device = griffin_lim_device
+        self._gl_dev_cache = {}
         self.sample_rate = sample_rate
         self.num_mels = num_mels
         self.min_level_db = min_level_db or 0
@@ -278,13 +286,87 @@ class AudioProcessor:
         return self._normalize(self._amp_to_db(self.mel_basis @ np.abs(self._preemph_stft(y))))
 
     def inv_melspectrogram(self, mel, rng=None):
-        """audio.py:241-248 (no pre-emphasis path: raise as the reference would need scipy lfilter)."""
+        """audio.py:241-248 (no pre-emphasis path: raise as the reference would need scipy lfilter).
+        With ``griffin_lim_device == "gpu"`` the batched GPU path runs at B = 1 (fp32; the phase is
+        ``rng.rand(n_freq, M)`` when an ``rng`` is given) and the result comes back as numpy."""
+        if self.griffin_lim_device == "gpu":
+            mel = np.asarray(mel, np.float32)
+            phase = None
+            if rng is not None:
+                u = np.asarray(rng.rand(self.fft_size // 2 + 1, mel.shape[1]), np.float32)
+                phase = torch.from_numpy(np.ascontiguousarray(u.T)[None]).cuda()
+            mels = torch.from_numpy(np.ascontiguousarray(mel.T)[None]).cuda()
+            wav, _ = self.inv_melspectrogram_batch(mels, [mel.shape[1]], phase)
+            wav = wav[0].cpu().numpy()
+            if self.preemphasis != 0:
+                import scipy.signal
+                return scipy.signal.lfilter([1], [1, -self.preemphasis], wav)
+            return wav
         S = self._db_to_amp(self._denormalize(mel))
         S = np.maximum(1e-10, self.inv_mel_basis @ S)
         if self.preemphasis != 0:
             import scipy.signal
             return scipy.signal.lfilter([1], [1, -self.preemphasis], self._griffin_lim(S ** self.power, rng))
         return self._griffin_lim(S ** self.power, rng)
+
+    # -- batched Griffin-Lim on the GPU (tts_mel_to_linear + tts_griffin_lim)
+    def _denorm_affine(self):
+        """`_denormalize` on a mel as dB = clip(x) * scale + offset per channel: (scale, offset, clip)
+        with clip None or the (lo, hi) bounds."""
+        ones = np.ones(self.num_mels)
+        if not self.signal_norm:
+            return ones, 0.0 * ones, None
+        if hasattr(self, "mel_scaler"):
+            return np.asarray(self.mel_scaler.scale_, np.float64), np.asarray(self.mel_scaler.mean_, np.float64), None
+        if self.symmetric_norm:
+            scale = -self.min_level_db / (2 * self.max_norm)
+            offset = self.max_norm * scale + self.min_level_db + self.ref_level_db
+            clip = (-self.max_norm, self.max_norm) if self.clip_norm else None
+        else:
+            scale = -self.min_level_db / self.max_norm
+            offset = self.min_level_db + self.ref_level_db
+            clip = (0.0, self.max_norm) if self.clip_norm else None
+        return scale * ones, offset * ones, clip
+
+    def _gl_check_params(self):
+        """What the GPU Griffin-Lim covers (include/ttship.h, tts_griffin_lim)."""
+        if self.stft_pad_mode != "reflect":
+            raise NotImplementedError(f"GPU Griffin-Lim: stft_pad_mode={self.stft_pad_mode!r} (only 'reflect')")
+        if self.fft_size != 1024:
+            raise NotImplementedError(f"GPU Griffin-Lim: fft_size={self.fft_size} (only 1024)")
+        if not 64 <= self.hop_length <= 512:
+            raise NotImplementedError(f"GPU Griffin-Lim: hop_length={self.hop_length} (64 to 512)")
+
+    def inv_melspectrogram_batch(self, mels, lengths, phase=None):
+        """`inv_melspectrogram` of a batch on the GPU, without the pre-emphasis inverse: ``mels``
+        (B, M_max, num_mels) normalised mels on a ROCm device, frame-major, row b valid for
+        ``lengths[b]`` frames; ``phase`` (B, M_max, fft_size / 2 + 1) uniform [0, 1) numbers (drawn
+        with torch.rand on the device when None). Returns the (B, hop_length * (M_max - 1)) device
+        tensor (rows zero past their own length) and the per-row sample counts."""
+        from ._lib import get_engine
+        self._gl_check_params()
+        eng = get_engine(mels.device)
+        dev = mels.device
+        if dev not in self._gl_dev_cache:
+            scale, offset, clip = self._denorm_affine()
+            put = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)  # noqa: E731
+            self._gl_dev_cache[dev] = (put(self.inv_mel_basis), put(scale), put(offset), clip)
+        inv_basis, scale, offset, clip = self._gl_dev_cache[dev]
+        mels = mels.contiguous().float()
+        B, M, _ = mels.shape
+        lengths = [int(n) for n in lengths]
+        F = self.fft_size // 2 + 1
+        S = torch.empty(B, M, F, device=dev)
+        if phase is None:
+            phase = torch.rand(B, M, F, device=dev)
+        phase = phase.contiguous().float()
+        assert phase.shape == S.shape and phase.device == dev
+        wav = torch.empty(B, self.hop_length * (M - 1), device=dev)
+        with eng.lock:
+            eng.mel_to_linear(mels, lengths, inv_basis, scale, offset, clip, self.spec_gain, self.power, S)
+            eng.griffin_lim(S, lengths, self.fft_size, self.win_length, self.hop_length, self.griffin_lim_iters,
+                            phase, wav)
+        return wav, [self.hop_length * (n - 1) for n in lengths]
 
     # -- trimming / saving (audio.py:302-341)
     def find_endpoint(self, wav, threshold_db=-40, min_silence_sec=0.8):

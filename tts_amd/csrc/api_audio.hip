@@ -1,0 +1,116 @@
+// Audio post-processing entry points: mel -> linear magnitudes and batched Griffin-Lim
+// (griffin_lim.hip). Both only enqueue work: no host synchronisation, no graph capture.
+#include "host.h"
+
+#include <cmath>
+
+using namespace ttsh;
+
+namespace {
+
+// The frame of a stream-asynchronous entry point: argument checks before anything touches a
+// device or a stream, then the work on c->s between the two stream joins.
+template <class Pre, class F>
+int async_call(tts_ctx* c, void* stream, Pre&& pre, F&& fn) {
+  return guarded_ctx(c, [&] {
+    pre();
+    DeviceGuard g(c->device);
+    enter(c, stream);
+    fn();
+    leave(c, stream);
+  });
+}
+
+GlLens lens_arg(const int32_t* h_lens, int B) {
+  GlLens L{};
+  for (int b = 0; b < B; ++b) L.v[b] = h_lens[b];
+  return L;
+}
+
+// twiddles e^{-2 pi i m / 1024} and the periodic Hann window of win_length points, centred in
+// 1024 as torch.stft pads it; computed in double, uploaded once per win_length
+void gl_tables(tts_ctx* c, int win_length) {
+  AudioWS& A = c->aws;
+  if (A.win_length == win_length) return;
+  const int N = 1024;
+  if (!A.W.p) {
+    std::vector<float> W(2 * N);
+    for (int m = 0; m < N; ++m) {
+      W[2 * m] = (float)std::cos(-2.0 * M_PI * m / N);
+      W[2 * m + 1] = (float)std::sin(-2.0 * M_PI * m / N);
+    }
+    A.W.upload(W);
+  }
+  std::vector<float> win(N, 0.f);
+  const int lo = (N - win_length) / 2;
+  for (int n = 0; n < win_length; ++n) win[lo + n] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * n / win_length));
+  HIP_OK(hipStreamSynchronize(c->s));  // a queued call may still read the previous window
+  A.win.upload(win);
+  A.win_length = win_length;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tts_mel_to_linear(tts_ctx* c, const float* d_mel, const int32_t* h_lens, int B, int M_max, int n_mels, int n_freq,
+                      const float* d_inv_basis, const float* d_scale, const float* d_offset, float clip_lo,
+                      float clip_hi, int use_clip, float spec_gain, float power, float* d_S, void* stream) {
+  return async_call(
+      c, stream,
+      [&] {
+        TTS_CHECK(d_mel && h_lens && d_inv_basis && d_scale && d_offset && d_S, "null argument");
+        TTS_CHECK(B >= 1 && B <= BMAX, "mel_to_linear: 1 <= B <= 64");
+        TTS_CHECK(M_max >= 1 && n_freq >= 1, "mel_to_linear: M_max and n_freq must be positive");
+        TTS_CHECK(n_mels >= 1 && n_mels <= 512, "mel_to_linear: 1 <= n_mels <= 512");
+        TTS_CHECK(spec_gain != 0.f, "mel_to_linear: spec_gain must not be 0");
+        for (int b = 0; b < B; ++b)
+          TTS_CHECK(h_lens[b] >= 0 && h_lens[b] <= M_max, "mel_to_linear: h_lens[b] outside [0, M_max]");
+      },
+      [&] {
+        launch_mel_to_linear(d_mel, lens_arg(h_lens, B), B, M_max, n_mels, n_freq, d_inv_basis, d_scale, d_offset,
+                             clip_lo, clip_hi, use_clip, spec_gain, power, d_S, c->s);
+      });
+}
+
+int tts_griffin_lim(tts_ctx* c, const float* d_S, const int32_t* h_lens, int B, int M_max, int n_fft, int win_length,
+                    int hop_length, int iters, const float* d_phase0, float* d_wav, void* stream) {
+  return async_call(
+      c, stream,
+      [&] {
+        TTS_CHECK(d_S && h_lens && d_phase0 && d_wav, "null argument");
+        TTS_CHECK(B >= 1 && B <= BMAX, "griffin_lim: 1 <= B <= 64");
+        TTS_CHECK(n_fft == 1024, "griffin_lim: n_fft must be 1024");
+        TTS_CHECK(win_length >= 1 && win_length <= n_fft, "griffin_lim: win_length outside [1, 1024]");
+        TTS_CHECK(hop_length >= 64 && hop_length <= 512, "griffin_lim: hop_length outside [64, 512]");
+        TTS_CHECK(iters >= 0, "griffin_lim: iters must be >= 0");
+        TTS_CHECK(M_max >= 1 && (long)hop_length * M_max < (1L << 30), "griffin_lim: M_max out of range");
+        for (int b = 0; b < B; ++b)
+          TTS_CHECK(h_lens[b] >= 1 && h_lens[b] <= M_max && hop_length * (h_lens[b] - 1) > n_fft / 2,
+                    "griffin_lim: every row needs h_lens[b] <= M_max and hop_length * (h_lens[b] - 1) > n_fft / 2 "
+                    "(the reflect padding of torch.stft)");
+      },
+      [&] {
+        AudioWS& A = c->aws;
+        gl_tables(c, win_length);
+        const size_t frames = (size_t)B * M_max * 1024 * sizeof(float);
+        const long env_stride = (long)hop_length * (M_max - 1) + 1024;
+        A.fa.ensure(frames);
+        A.fb.ensure(frames);
+        A.env.ensure((size_t)B * env_stride * sizeof(float));
+        const GlLens L = lens_arg(h_lens, B);
+        const int wlo = (1024 - win_length) / 2, whi = wlo + win_length;
+        float *cur = A.fa.f(), *nxt = A.fb.f();
+        launch_gl_env(A.env.f(), A.win.f(), L, B, M_max, hop_length, wlo, whi, env_stride, c->s);
+        launch_gl_frames(true, d_S, d_phase0, nullptr, cur, A.env.f(), A.W.f(), A.win.f(), L, B, M_max, hop_length, wlo,
+                         whi, env_stride, c->s);
+        for (int i = 0; i < iters; ++i) {
+          launch_gl_frames(false, d_S, nullptr, cur, nxt, A.env.f(), A.W.f(), A.win.f(), L, B, M_max, hop_length, wlo,
+                           whi, env_stride, c->s);
+          std::swap(cur, nxt);
+        }
+        launch_gl_finish(cur, A.env.f(), d_wav, L, B, M_max, hop_length, wlo, whi, env_stride, c->s);
+      });
+}
+
+}  // extern "C"

@@ -318,6 +318,13 @@ struct PwganWS {
   DevBuf lens, ca, cb, xa, xb, skip, zeros;
 };
 
+// Griffin-Lim (griffin_lim.hip): twiddles, the window of the last call's win_length, the two
+// ping-pong frame buffers (B, M_max, 1024) and the rows' window-square envelopes
+struct AudioWS {
+  DevBuf W, win, fa, fb, env;
+  int win_length = -1;
+};
+
 // one submitted fused call: what its fp32 re-run needs if the split-f16 vocoder raised the range
 // flag (the caller keeps d_post and d_wav untouched until the ticket is finished)
 constexpr int NVT = 4, TK_PIN = 248;
@@ -369,6 +376,7 @@ struct tts_ctx {
   ttsh::HostMap glow_host;
   ttsh::GlowModel glow;
   ttsh::GlowWS glws;
+  ttsh::AudioWS aws;
   // last decode configuration (for tts_time_decoder_kernel)
   int last_B = 0, last_T = 0, last_S = 0, last_r = 0;
   // fused Tacotron2 + MB-MelGAN submissions whose vocoder may still run (tts_taco_mbmelgan_submit)

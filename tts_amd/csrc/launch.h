@@ -53,3 +53,21 @@ void pack_pw_layer_x3(const std::vector<float>& m1, const std::vector<float>& m2
 void launch_pw_out(const float* skip, float scale, const float* W3, const float* b3, const float* w4,
                    const float* b4, const int* lens, int len_add, int hop, int Tmax, float* out, int B,
                    hipStream_t st);
+
+// griffin_lim.hip. Row lengths travel as a kernel argument (at most 64 rows), so a call needs no
+// host-to-device copy. W = e^{-2 pi i m / 1024} (1024 complex), win = the window zero-padded to
+// 1024, nonzero inside [wlo, whi); env (B, env_stride) the rows' window-square envelopes; F
+// (B, M_max, 1024) windowed frames.
+struct GlLens {
+  int v[64];
+};
+void launch_gl_env(float* env, const float* win, const GlLens& lens, int B, int M_max, int hop, int wlo, int whi,
+                   long env_stride, hipStream_t s);
+void launch_gl_frames(bool start, const float* S, const float* u, const float* Fin, float* Fout, const float* env,
+                      const float* W, const float* win, const GlLens& lens, int B, int M_max, int hop, int wlo,
+                      int whi, long env_stride, hipStream_t s);
+void launch_gl_finish(const float* F, const float* env, float* wav, const GlLens& lens, int B, int M_max, int hop,
+                      int wlo, int whi, long env_stride, hipStream_t s);
+void launch_mel_to_linear(const float* mel, const GlLens& lens, int B, int M_max, int n_mels, int F, const float* inv,
+                          const float* scale, const float* offset, float clip_lo, float clip_hi, int use_clip,
+                          float spec_gain, float power, float* S, hipStream_t s);

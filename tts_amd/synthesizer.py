@@ -5,7 +5,8 @@ Follows `TTS/server/synthesizer.py:21-193`. What differs on purpose:
     vocoder call (the reference loops B=1 per sentence, because its decoder cannot batch,
     `TTS/tts/layers/tacotron2.py:362`); per-sentence outputs are cut back to each sentence's
     own mel length, so every sentence equals its B=1 synthesis;
-  * without a vocoder checkpoint the Griffin-Lim fallback runs on the CPU (`tts_amd.audio`);
+  * without a vocoder checkpoint the Griffin-Lim fallback runs on the CPU (`tts_amd.audio`), or, with
+    ``"griffin_lim_device": "gpu"`` in the audio config, batched on the GPU from the postnet output;
   * checkpoints load with `torch.load(..., weights_only=True)`;
   * sentence splitting and the text front end are the stand-ins of `tts_amd.text` (pysbd,
     phonemizer, unidecode and inflect are not in this image); phoneme configs need a
@@ -160,6 +161,15 @@ class Synthesizer:
                 hop = wav.shape[-1] // post.shape[1]
                 wav = wav.reshape(len(seqs), -1).cpu().numpy()
                 return [wav[i, :mel_lens[i] * hop] for i in range(len(seqs))]
+            if self.ap.griffin_lim_device == "gpu":
+                # Griffin-Lim on the device, on the postnet rows in place (no host copy of the mels)
+                wav, counts = self.ap.inv_melspectrogram_batch(post, mel_lens)
+                wav = wav.cpu().numpy()
+                if self.ap.preemphasis != 0:
+                    import scipy.signal
+                    return [scipy.signal.lfilter([1], [1, -self.ap.preemphasis], wav[i, :n]).astype(np.float32)
+                            for i, n in enumerate(counts)]
+                return [wav[i, :n] for i, n in enumerate(counts)]
         post = post.cpu().numpy()
         return [self.ap.inv_melspectrogram(post[i, :mel_lens[i]].T).astype(np.float32) for i in range(len(seqs))]
 
