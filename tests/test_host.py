@@ -336,3 +336,27 @@ def test_single_speaker_model_ignores_speaker_arguments(monkeypatch):
                     max_decoder_steps=3)
     for x, y in zip(a, b):
         assert torch.equal(x, y)
+
+
+def test_runtime_switch_table_matches_switches_header():
+    """tts_amd/csrc/switches.h is the one place the library reads its environment: the TTS_* names in
+    its string literals are exactly the rows of INTEGRATION.md's "Run-time switches" table, and no
+    other file under tts_amd/csrc/ calls getenv."""
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "tts_amd", "csrc")
+    header = open(os.path.join(csrc, "switches.h")).read()
+    in_header = set()
+    for lit in re.findall(r'"((?:[^"\\\n]|\\.)*)"', header):
+        in_header.update(re.findall(r"TTS_[A-Z0-9_]+", lit))
+    doc = open(os.path.join(root, "INTEGRATION.md")).read()
+    section = doc.split("### Run-time switches", 1)[1].split("\n## ", 1)[0]
+    in_table = set()
+    for row in section.splitlines():
+        if row.startswith("| `"):  # the name is the first cell
+            in_table.update(re.findall(r"TTS_[A-Z0-9_]+", row.split("|")[1]))
+    assert in_header and in_header == in_table, (sorted(in_header - in_table), sorted(in_table - in_header))
+    others = [f for f in sorted(os.listdir(csrc))
+              if f != "switches.h" and os.path.isfile(os.path.join(csrc, f))
+              and "getenv" in open(os.path.join(csrc, f), errors="ignore").read()]
+    assert others == [], others

@@ -2,9 +2,9 @@
 // (host.h): tensor staging, weight layout, conv layer packing and launching, stream ordering.
 #include "host.h"
 #include "split16.h"
+#include "switches.h"
 
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 #include <memory>
 
@@ -267,11 +267,10 @@ int tts_ctx_create(int device, tts_ctx** out) {
     TTS_CHECK(device >= 0 && device < n, "invalid device");
     auto c = std::make_unique<tts_ctx>();
     c->device = device;
-    if (const char* e = std::getenv("TTS_GEMM")) c->gemm_x3 = std::string(e) != "f32";
+    c->gemm_x3 = !sw::gemm_f32();
     DeviceGuard g(device);
     HIP_OK(hipStreamCreateWithFlags(&c->s, hipStreamNonBlocking));
-    const char* vs = std::getenv("TTS_VOC_STREAM");
-    if (vs && std::atoi(vs) == 0) c->sv = c->s;
+    if (!sw::voc_stream()) c->sv = c->s;
     else HIP_OK(hipStreamCreateWithFlags(&c->sv, hipStreamNonBlocking));
     HIP_OK(hipEventCreateWithFlags(&c->ev_sv, hipEventDisableTiming));
     HIP_OK(hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming));

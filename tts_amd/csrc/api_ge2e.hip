@@ -2,9 +2,9 @@
 #include "host.h"
 #include "gsync.h"
 #include "split16.h"
+#include "switches.h"
 
 #include <cmath>
-#include <cstdlib>
 
 using namespace ttsh;
 
@@ -157,10 +157,7 @@ void ge2e_infer(tts_ctx* c, const float* d_x, const int32_t* h_lens, int B, int 
   int din = G.in_pad;
   // all layers in one persistent launch (encoder.hip ge2e_pipe_kernel); TTS_GE2E_PIPE=0 keeps
   // one launch per layer with the input projections as convs
-  static const bool pipe_env = [] {
-    const char* e = std::getenv("TTS_GE2E_PIPE");
-    return !(e && std::string(e) == "0");
-  }();
+  const bool pipe_env = sw::ge2e_pipe();
   bool piped = false;
   if (pipe_env && c->gemm_x3 && G.pipe_ok && B <= 16) {
     ConvCall cc;  // layer-0 input gates

@@ -2,9 +2,9 @@
 // tts_melgan_* entry points.
 #include "host.h"
 #include "split16.h"
+#include "switches.h"
 
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 
 using namespace ttsh;
@@ -135,36 +135,6 @@ static void melgan_finalize(tts_ctx* c, int in_ch, int out_ch, int base, const i
   G.ready = true;
 }
 
-// blocks 0-2 of a C = 48 ResidualStack as one kernel (TTS_STACK_FUSE=0: block by block, for A/B)
-static bool stack_fuse_on() {
-  static const bool on = [] {
-    const char* e = std::getenv("TTS_STACK_FUSE");
-    return !e || std::atoi(e) != 0;
-  }();
-  return on;
-}
-// the C = 96 stack in one launch: off by default since round 5 (TTS_STACK_FUSE96=1 turns it on).
-// Same-box A/B over 4 bench runs each (profiles/r05/v17_stack96_ab.txt): vocoder 2.958 ms fused
-// against 2.922 ms with blocks 0-2 as three resblock_x3 launches; the stack kernel's halo
-// recompute (up to 24 extra rows per 96-position tile) now costs more than the two HBM round trips
-// of x it saves at this width, while at C = 48 (with the fused ConvTranspose) fusing still wins
-static bool stack_fuse96_on() {
-  static const bool on = [] {
-    const char* e = std::getenv("TTS_STACK_FUSE96");
-    return e && std::atoi(e) != 0;
-  }();
-  return on;
-}
-// the last upsample's ConvTranspose inside the C = 48 stack kernel (resstack_x3.hip CTU = 2);
-// TTS_CT_FUSE=0 keeps the separate conv_x3 launch
-static bool ct_fuse_on() {
-  static const bool on = [] {
-    const char* e = std::getenv("TTS_CT_FUSE");
-    return !e || std::atoi(e) != 0;
-  }();
-  return on;
-}
-
 int ttsh::run_generator(tts_ctx* c, const float* mel, const int32_t* h_lens, int B, int M_max, int pad, float* out,
                   hipStream_t s, GenTail* tail, const int64_t* mel_strides, bool dev_lens) {
   auto& G = c->mg;
@@ -235,8 +205,8 @@ int ttsh::run_generator(tts_ctx* c, const float* mel, const int32_t* h_lens, int
   // ConvTranspose input and the kernel computes the stage input per tile): false if not covered
   auto stack3 = [&](size_t i, int Cs, long Lss, int muls, const float* xs, float* ys, const ConvLayer* ct,
                     const float* xin, int Cin, long Lin) {
-    if (!(cc.oflow && G.nres >= 3 && stack_fuse_on() && G.rb_wd16[i * G.nres].p)) return false;
-    if (Cs == 96 && !stack_fuse96_on()) return false;
+    if (!(cc.oflow && G.nres >= 3 && sw::stack_fuse() && G.rb_wd16[i * G.nres].p)) return false;
+    if (Cs == 96 && !sw::stack_fuse96()) return false;
     int dil[3];
     for (int k = 0; k < 3; ++k) dil[k] = G.dconv[i * G.nres + k].dil;
     if (!resstack_x3_supported(Cs, dil, 3)) return false;
@@ -271,7 +241,7 @@ int ttsh::run_generator(tts_ctx* c, const float* mel, const int32_t* h_lens, int
   for (size_t i = 0; i < G.ups.size(); ++i) {
     const int u = G.ups[i];
     int bk0 = 0;
-    if (u == 2 && C == 96 && ct_fuse_on() && cc.oflow && G.convTm[i].W16.p &&
+    if (u == 2 && C == 96 && sw::ct_fuse() && cc.oflow && G.convTm[i].W16.p &&
         stack3(i, C / 2, Ls * u, mul * u, nullptr, xo, &G.convTm[i], x, C, Ls)) {
       // LeakyReLU + ConvTranspose1d + blocks 0-2 in one launch (resstack_x3.hip CTU = 2)
       std::swap(x, xo);

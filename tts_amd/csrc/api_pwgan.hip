@@ -1,9 +1,9 @@
 // ParallelWaveGAN: weight packing, the generator, and the tts_pwgan_* entry points.
 #include "host.h"
 #include "split16.h"
+#include "switches.h"
 
 #include <cmath>
-#include <cstdlib>
 
 using namespace ttsh;
 
@@ -151,12 +151,7 @@ void pwgan_infer(tts_ctx* c, const float* mel, const int32_t* h_lens, int B, int
     HIP_OK(hipMemsetAsync(W.zeros.p, 0, 256 * 4, s));
   }
   // residual-block kernel: LDS-DMA ring (default) or register staging (TTS_PWGAN_STAGING=regs)
-  static const int variant = [] {
-    const char* e = std::getenv("TTS_PWGAN_STAGING");
-    if (e && std::string(e) == "regs") return 0;
-    if (e && std::string(e) == "ring4") return 2;
-    return 1;
-  }();
+  const int variant = sw::pwgan_staging();
   const int per_stack = P.layers / P.stacks;
   unsigned* flag = x3_flag(c);
   for (int l = 0; l < P.layers; ++l) {

@@ -4,9 +4,9 @@
 #include "decoder.h"
 #include "gsync.h"
 #include "split16.h"
+#include "switches.h"
 
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 
 using namespace ttsh;
@@ -260,8 +260,7 @@ void run_encoder(tts_ctx* c, const int64_t* ids, int B, int T_max, float* enc_ou
   // one cooperative launch for the whole recurrence (W.lc then holds its grid-barrier words; its
   // fill zeroes enc_out too); per-step launches when cooperative launch is unavailable or
   // TTS_ENCODER=steps
-  const char* e = std::getenv("TTS_ENCODER");
-  W.enc_ndom = (e && std::string(e) == "steps")
+  W.enc_ndom = sw::encoder_steps()
                    ? 0
                    : launch_bilstm_persist(W.gin.f(), M.whhT.f(), c->gemm_x3 ? M.whhT16.h() : nullptr, lens, T_max, B,
                                            W.lh.f(), reinterpret_cast<unsigned*>(W.lc.p), enc_out, s);
@@ -467,8 +466,7 @@ hipGraphExec_t step_graph(tts_ctx* c, int MT, hipStream_t s) {
 }
 
 bool use_persistent(tts_ctx* c) {
-  const char* e = std::getenv("TTS_DECODER");
-  if (e && std::string(e) == "graph") return false;
+  if (sw::decoder_graph()) return false;
   return c->tws.MT <= PMAX_LAUNCH && persist_supported(c->device);
 }
 
@@ -486,7 +484,7 @@ void run_persistent(tts_ctx* c, int r, float thr, hipStream_t s) {
   a.x3flag = x3_flag(c);  // null in fp32 mode
   // split-f16 decoder GEMM parts: only with every split weight set in range, and Q = 1024,
   // E = 512, prenet 256 (the kernel's fixed geometry, checked by build_pj's callers)
-  const bool dx3 = a.x3flag && M.att_p_x3.p && M.dec_x3.p && M.apre_x3.p && M.pj_x3.p && !std::getenv("TTS_DECODER_F32");
+  const bool dx3 = a.x3flag && M.att_p_x3.p && M.dec_x3.p && M.apre_x3.p && M.pj_x3.p && !sw::decoder_f32();
   a.attp_x3 = dx3 ? M.att_p_x3.h() : nullptr;
   a.dec_x3 = dx3 ? M.dec_x3.h() : nullptr;
   a.apre_x3 = dx3 ? M.apre_x3.h() : nullptr;
@@ -574,13 +572,13 @@ void run_persistent(tts_ctx* c, int r, float thr, hipStream_t s) {
   a.counter = reinterpret_cast<unsigned*>(W.acnt.p);
   a.nchmax = (W.T_max + persist_attn_tc() - 1) / persist_attn_tc();
   a.anorm = W.anorm.f();
-  a.defer_align = persist_defer_ok(W.B * a.nchmax) && !std::getenv("TTS_ALIGN_IN_P4");
+  a.defer_align = persist_defer_ok(W.B * a.nchmax) && !sw::align_in_p4();
   a.softmax = M.softmax;
   a.thr = thr;
   a.bar = reinterpret_cast<unsigned*>(W.pbar.p);
   // TTS_PTRACE=<file>: phase timestamps of 8 steps from step TTS_PTRACE_T0 (default 100)
   DevBuf& trace_buf = W.trace;
-  const char* tr = std::getenv("TTS_PTRACE");
+  const char* tr = sw::ptrace_file();
   TTS_CHECK(!tr || persist_trace_built(), "TTS_PTRACE needs a library built with -DTTS_PHASE_TRACE "
                                           "(tools/build_variants.sh trace -DTTS_PHASE_TRACE; TTSHIP_LIB=tools/var/lib_trace.so)");
   if (tr) {
@@ -588,17 +586,12 @@ void run_persistent(tts_ctx* c, int r, float thr, hipStream_t s) {
     HIP_OK(hipMemsetAsync(trace_buf.p, 0, (size_t)8 * 24 * 256 * 8, s));
     a.trace = static_cast<unsigned long long*>(trace_buf.p);
     a.atrace = a.trace + (size_t)8 * 16 * 256;
-    const char* t0 = std::getenv("TTS_PTRACE_T0");
-    a.trace_t0 = t0 ? std::atoi(t0) : 100;
+    a.trace_t0 = sw::ptrace_t0();
   }
-  // TTS_PTRACE_LAUNCH: which launch of the MT cascade is traced (default 0, the first)
-  const int trace_li = [] {
-    const char* e = std::getenv("TTS_PTRACE_LAUNCH");
-    return e ? std::atoi(e) : 0;
-  }();
+  const int trace_li = sw::ptrace_launch();
   unsigned long long* const trace_p = a.trace;
   unsigned long long* const atrace_p = a.atrace;
-  static const bool xdiag = std::getenv("TTS_DIAG_XCC") != nullptr;
+  const bool xdiag = sw::diag_xcc();
   DevBuf& xdiag_buf = W.xdiag;
   if (xdiag) xdiag_buf.ensure((size_t)PMAX_LAUNCH * 256 * 4);
   c->dec_nlaunch = 0;

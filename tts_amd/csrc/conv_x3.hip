@@ -26,18 +26,15 @@
 #include "common.h"
 #include "conv_epi.h"
 #include "split16.h"
+#include "switches.h"
+#include "x3_tile.h"
 
-#include <cstdlib>
 #include <algorithm>
 #include <mutex>
 #include <map>
 
 namespace {
 constexpr int CX_XR = 80;  // staging row, halves: 32 hi | 32 lo | 16 pad (160 B)
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t cx_rsrc(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000);
-}
 }  // namespace
 
 template <int MI, int NI, int WM, int WN, int KT, int RS, int SD>
@@ -154,7 +151,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_x3_kernel(ConvArgs a, int n
   };
 
   // ---- weights: RS-slot ring over the flattened k-step sequence ----
-  const __amdgpu_buffer_rsrc_t wr = cx_rsrc(reinterpret_cast<const char*>(a.W16) + (long)ph * a.w16_phase_stride);
+  const __amdgpu_buffer_rsrc_t wr = x3_rsrc(reinterpret_cast<const char*>(a.W16) + (long)ph * a.w16_phase_stride);
   const int wlo = lane * 32;
   const int mt0 = co0 / 16 + wm * MI;
   h8 ring[RS][MI][2];
@@ -164,8 +161,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_x3_kernel(ConvArgs a, int n
     for (int mi = 0; mi < MI; ++mi) {
       const int mt = min(mt0 + mi, mtiles - 1);  // rows past Cout: discarded by the epilogue
       const int so = (mt * NKS + ks) * 2048;
-      r[mi][0] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(wr, wlo, so, 0));
-      r[mi][1] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(wr, wlo + 16, so, 0));
+      x3_load_a(r[mi], wr, wlo, so);
     }
   };
 
@@ -434,10 +430,7 @@ void launch_conv_x3(const ConvArgs& a, hipStream_t s) {
       // 512 -> 512 176.1 / 180.5 us, upsample 1 173.2 / 197.4 us, upsample 2 208.6 / 226.7 us;
       // Glow-TTS (WN convs 192 -> 384, 8 k squeezed frames: 513 tiles on 512 slots at 48 wide)
       // 4.75 / 4.44 ms per call. TTS_CX_NI128 = 3 / 4 forces one width (A/B builds).
-      static const int force = [] {
-        const char* e = std::getenv("TTS_CX_NI128");
-        return e ? std::atoi(e) : 0;
-      }();
+      const int force = sw::cx_ni128();
       bool narrow = force == 3;
       if (!force && a.K >= 2) narrow = cx_cost<2, 3, 4, 1, 2>(a) < cx_cost<2, 4, 4, 1, 2>(a);
       if (narrow) cx_taps<2, 3, 4, 1, 2>(a, s);

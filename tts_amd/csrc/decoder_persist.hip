@@ -41,16 +41,8 @@
 
 namespace {
 constexpr int PW = 256, PT = 512, NWV = 8;
-// the step's grid barriers: gsync.h's flag barrier (one store per arrival, workgroup 0 releases);
-// -DTTS_BAR_COUNTERS builds the counter form for A/B
-#ifdef TTS_BAR_COUNTERS
-#define BAR_ARRIVE gsync_arrive
-#define BAR_WAIT gsync_wait
-#else
+// the step's grid barriers: gsync.h's flag barrier (one store per arrival, workgroup 0 releases)
 static_assert(PW <= 256, "gflag barrier: one flag word per workgroup, 256 at most");
-#define BAR_ARRIVE gflag_arrive
-#define BAR_WAIT gflag_wait
-#endif
 constexpr int DEC_NC = 20;   // 160 k-chunks / 8 waves
 constexpr int ATTP_NC = 8;   // 4 tiles x 16 chunks / 8 waves
 constexpr int PJ_NC = 6;     // 48 / 8
@@ -72,11 +64,7 @@ constexpr int pec_arr(int VAR, int MT) { return pec_of(VAR, MT) > 0 ? pec_of(VAR
 // fragment quad takes in fp32, so the streaming consumers feed the loads to the MFMA without
 // splitting (the split is done once, by the producer; tools/payload_bench.hip mode 3: 0.42 us less
 // per streamed 192 KB block). The variants with fp32 readers of these buffers keep fp32.
-#ifdef TTS_NO_PRESPLIT
-constexpr bool presplit_of(int) { return false; }
-#else
 constexpr bool presplit_of(int VAR) { return VAR == 8; }
-#endif
 template <bool PS>
 __device__ __forceinline__ void stc_quad_h(float* base, int e, float v) {
   if constexpr (PS) stc_quad_x3(base, e, v);
@@ -96,19 +84,10 @@ constexpr int LOCK_ = 31, ADIM_ = 128, NPQ_ = NATT;  // NPQ_: query-projection p
 // * split-f16 weight / operand fragments in LDS as [k-step][hi 64 lanes | lo 64 lanes] planes: a
 //   lane's 16-byte read is contiguous with its neighbours' (the interleaved [lane][hi | lo] form
 //   strides lanes 32 B apart: 2-way on every ds_read_b128 / ds_write_b128).
-#ifndef TTS_RS
-#define TTS_RS 20
-#endif
-#ifndef TTS_WCLD
-#define TTS_WCLD 144
-#endif
-#ifndef TTS_X3_PLANES
-#define TTS_X3_PLANES 1
-#endif
-constexpr int RS = TTS_RS, WCLD = TTS_WCLD;
+constexpr int RS = 20, WCLD = 144;
 // LDS index (in 16-byte units) of the hi (h = 0) / lo (h = 1) half of lane `lane`'s split fragment of k-step ks
 __device__ __forceinline__ int x3i(int ks, int lane, int h) {
-  return TTS_X3_PLANES ? (ks * 128 + h * 64 + lane) : ((ks * 64 + lane) * 2 + h);
+  return ks * 128 + h * 64 + lane;
 }
 }  // namespace
 
@@ -1235,7 +1214,7 @@ __global__ __launch_bounds__(PT) void persist_decoder_kernel(PArgs P) {
       }
     }
     PTRACE(1);
-    BAR_ARRIVE(P.bar, gen);
+    gflag_arrive(P.bar, gen);
     // P3 operands that are already final: its epilogue's gate addends (written by P5 of the
     // previous step), c_att, the query-projection weights
     float ga[NCK][4], ca[NCK], wq[4];
@@ -1271,7 +1250,7 @@ __global__ __launch_bounds__(PT) void persist_decoder_kernel(PArgs P) {
 #pragma unroll
       for (int i = 0; i < ATTP_NC; ++i) wa[i] = src[(long)i * 64];
     }
-    if (!BAR_WAIT(P.bar, gen, &sflag)) return;
+    if (!gflag_wait(P.bar, gen, &sflag)) return;
     PTRACE(2);
     tid = opaque_v(tid0);
     lane = opaque_v(lane0);
@@ -1436,16 +1415,9 @@ __global__ __launch_bounds__(PT) void persist_decoder_kernel(PArgs P) {
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt)
             qa[mt] = MFMA16(wq[q], hs[(mt * 16 + (lane & 15)) * 17 + 4 * q + (lane >> 4)], qa[mt]);
-#ifdef TTS_PQ_NARROW
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) stc(P.pq + ((long)g * Bp + mt * 16 + (lane & 15)) * 128 + 16 * wave + 4 * (lane >> 4) + j, qa[mt][j]);
-#else
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
           stc4(P.pq, (((g * Bp + mt * 16 + (lane & 15)) * 128) + 16 * wave + 4 * (lane >> 4)) * 4, qa[mt]);
-#endif
       }
       PTRACE(12);
     } else {
@@ -1453,8 +1425,8 @@ __global__ __launch_bounds__(PT) void persist_decoder_kernel(PArgs P) {
       write_frames(t - 1, NATT, PW - NATT);
     }
     PTRACE(3);
-    BAR_ARRIVE(P.bar, gen);
-    if (!BAR_WAIT(P.bar, gen, &sflag)) return;
+    gflag_arrive(P.bar, gen);
+    if (!gflag_wait(P.bar, gen, &sflag)) return;
     if constexpr (GRAVES) {
       // ======== P3g: N_a hidden = relu(W1 h_att + b1), 16 units per workgroup IW0 .. IW0+63 ========
       tid = opaque_v(tid0);
@@ -1483,8 +1455,8 @@ __global__ __launch_bounds__(PT) void persist_decoder_kernel(PArgs P) {
           lds_barrier();
         }
       }
-      BAR_ARRIVE(P.bar, gen);
-      if (!BAR_WAIT(P.bar, gen, &sflag)) return;
+      gflag_arrive(P.bar, gen);
+      if (!gflag_wait(P.bar, gen, &sflag)) return;
     }
     PTRACE(4);
     // ======== P4: attention || the h_att parts of decoder_rnn and attention_rnn ========
@@ -1524,12 +1496,12 @@ __global__ __launch_bounds__(PT) void persist_decoder_kernel(PArgs P) {
       }
     }
     PTRACE(5);
-    BAR_ARRIVE(P.bar, gen);
+    gflag_arrive(P.bar, gen);
     // P5 epilogue operand (own tile's c_dec), fetched during the barrier
     float cd[NCK];
 #pragma unroll
     for (int c = 0; c < NCK; ++c) cd[c] = P.cdec[(long)min(c * CB + (tid >> 2), Bp - 1) * 1024 + g * 4 + (tid & 3)];
-    if (!BAR_WAIT(P.bar, gen, &sflag)) return;
+    if (!gflag_wait(P.bar, gen, &sflag)) return;
     PTRACE(6);
     // ======== P5: ctx parts, then the decoder_rnn cell (tile g) and the next step's
     //            attention_rnn ctx/h part (tile g, + biases) ========
@@ -1577,7 +1549,7 @@ __global__ __launch_bounds__(PT) void persist_decoder_kernel(PArgs P) {
       for (int mt = 0; mt < MT; ++mt) accd[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     PTRACE(7);
-    BAR_ARRIVE(P.bar, gen);
+    gflag_arrive(P.bar, gen);
     // projection weights for P6 (half pj & 1 of job tile pj >> 1, 6 k-chunks per wave)
     f32x4 wp[X3P ? 1 : PJ_NC];
     h8 wpx[X3P ? PJ_NC : 1][2];  // split-f16: the whole K for 16 rows, k-steps 6 wave .. + 5
@@ -1594,7 +1566,7 @@ __global__ __launch_bounds__(PT) void persist_decoder_kernel(PArgs P) {
         for (int i = 0; i < PJ_NC; ++i) wp[i] = src[(long)i * 64];
       }
     }
-    if (!BAR_WAIT(P.bar, gen, &sflag)) return;
+    if (!gflag_wait(P.bar, gen, &sflag)) return;
     PTRACE(8);
     // ======== P6: projection halves (workgroups PJ_WG0 ..) || attention_rnn h_att part (items) ========
     tid = opaque_v(tid0);
@@ -1691,8 +1663,8 @@ __global__ __launch_bounds__(PT) void persist_decoder_kernel(PArgs P) {
       }
     }
     PTRACE(9);
-    BAR_ARRIVE(P.bar, gen);
-    if (!BAR_WAIT(P.bar, gen, &sflag)) return;
+    gflag_arrive(P.bar, gen);
+    if (!gflag_wait(P.bar, gen, &sflag)) return;
   }
 }
 
@@ -1724,8 +1696,7 @@ __global__ __launch_bounds__(PT) void gflag_cal_kernel(unsigned* bar, int iters)
 
 void pick_barrier_blocks(unsigned* pool, int ncand, int nwant, int* slot, hipStream_t s) {
   for (int i = 0; i < nwant; ++i) slot[i] = i;
-  const char* e = std::getenv("TTS_BAR_CALIBRATE");
-  if ((e && std::atoi(e) == 0) || ncand <= nwant) return;
+  if (!sw::bar_calibrate() || ncand <= nwant) return;
   const void* f = (const void*)gflag_cal_kernel;
   ensure_dyn_lds(f, (int)P_LDS);  // one workgroup per CU, as the decoder
   hipEvent_t e0, e1;
@@ -1761,7 +1732,7 @@ void pick_barrier_blocks(unsigned* pool, int ncand, int nwant, int* slot, hipStr
   HIP_OK(hipEventDestroy(e1));
   std::stable_sort(t.begin(), t.end());
   for (int i = 0; i < nwant; ++i) slot[i] = t[i].second;
-  if (std::getenv("TTS_DIAG_XCC")) {
+  if (sw::diag_xcc()) {
     std::fprintf(stderr, "TTS_DIAG_XCC barrier blocks (us per barrier):");
     for (auto& x : t) std::fprintf(stderr, " %d:%.3f", x.second, x.first * 1000.f / iters);
     std::fprintf(stderr, "\n");

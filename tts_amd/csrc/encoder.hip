@@ -10,6 +10,7 @@
 #include "gsync.h"
 #include "launch.h"
 #include "split16.h"
+#include "switches.h"
 
 // row stride of the LDS gate-partial reductions [wave][row][LRS]: writers put rows r and r + 4 of a
 // 32-lane group 80 = 16 (mod 32) banks apart, the cell threads read rows m = tid / 4 (8 per group)
@@ -253,19 +254,11 @@ __global__ __launch_bounds__(64 * LSTM_NW) void lstm_persist_kernel(const float*
       // the recurrence's NT workgroups: counter form (tools/group_bar_bench.hip, 4 groups of 64
       // with the 16 KB h exchange: 2.41-2.51 us per step against 2.51-2.64 for the flag form,
       // which wins on the full 256-workgroup grid; the BiLSTM kernel itself reads the same with
-      // either, 531 / 528 us); -DTTS_LSTM_BAR_FLAGS builds the flag form
-#ifndef TTS_LSTM_BAR_FLAGS
+      // either, 531 / 528 us)
       gsync_arrive(db, gen, NT);
-#else
-      gflag_arrive(db, gen, tl);
-#endif
 #pragma unroll
       for (int q = 0; q < 4; ++q) gin[q] = gbase[(long)tpos(step + 1) * G + q * 4];
-#ifndef TTS_LSTM_BAR_FLAGS
       if (!gsync_wait(db, gen, &sflag)) return;
-#else
-      if (!gflag_wait(db, gen, &sflag, NT, tl)) return;
-#endif
     }
   }
 }
@@ -284,10 +277,7 @@ static int launch_lstm_persist_t(const float* Gin, const float* Whh, const uint1
   if (!coop) return 0;
   // row groups: two recurrences of half the batch tiles each when every workgroup of both still
   // fits the device (the encoder BiLSTM, B > 16: 2 x 2 x 64 = 256); TTS_LSTM_RG=1 turns it off
-  static const bool rg_on = [] {
-    const char* e = std::getenv("TTS_LSTM_RG");
-    return !e || std::atoi(e) != 1;
-  }();
+  const bool rg_on = sw::lstm_row_groups();
   const int MT0 = (B + 15) / 16;
   const int RG = (rg_on && MT0 % 2 == 0 && 2 * NDIR * (H / 4) <= device_cu_count()) ? 2 : 1;
   const int MT = MT0 / RG, Bp = MT * 16;

@@ -30,8 +30,8 @@
 #include "common.h"
 #include <hip/hip_ext.h>
 #include "split16.h"
+#include "switches.h"
 
-#include <cstdlib>
 #include <map>
 #include <mutex>
 #include <utility>
@@ -44,12 +44,7 @@ constexpr int BAR_WORDS = 1024;
 
 // entries zeroing `nblk` barrier blocks and writing their wait limit, for a caller's fill
 inline void add_barrier_fills(FillList& f, unsigned* bar, int nblk) {
-  static const unsigned ticks = [] {
-    double ms = 2000.0;
-    if (const char* e = std::getenv("TTS_BARRIER_TIMEOUT_MS")) ms = std::atof(e);
-    ms = ms < 1.0 ? 1.0 : (ms > 40000.0 ? 40000.0 : ms);
-    return (unsigned)(ms * 1e5);  // 100 MHz ticks
-  }();
+  const unsigned ticks = (unsigned)(sw::barrier_timeout_ms() * 1e5);  // 100 MHz ticks
   for (int i = 0; i < nblk; ++i) {
     f.add(bar + i * BAR_WORDS, BAR_TMO * 4);
     f.add(bar + i * BAR_WORDS + BAR_TMO, 4, ticks);
@@ -80,10 +75,7 @@ inline void launch_resident(const void* f, dim3 grid, dim3 block, void** args, s
                             hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr) {
   static std::mutex mu;
   static std::map<std::pair<const void*, int>, int> fits;  // (kernel, device) -> workgroups it holds at once
-  static const bool coop = [] {
-    const char* e = std::getenv("TTS_COOP_LAUNCH");
-    return e && std::atoi(e) != 0;
-  }();
+  const bool coop = sw::coop_launch();
   int cap = 0, dev = 0;
   HIP_OK(hipGetDevice(&dev));
   {
@@ -139,18 +131,14 @@ __device__ __forceinline__ void stc4(float* base, int off, f32x4 v) {
 
 // 4 consecutive elements held by the 4 lanes of a DPP quad (lane q of the quad: element e0 + q,
 // e0 % 4 == 0, every lane of the quad active): gathered into the quad's lane 0 and written as ONE
-// 16-byte coherent store. TTS_NARROW_STORES keeps the per-lane 4-byte stores (A/B builds).
+// 16-byte coherent store.
 __device__ __forceinline__ void stc_quad(float* base, int e, float v) {
-#ifdef TTS_NARROW_STORES
-  stc(base + e, v);
-#else
   const int b = __float_as_int(v);
   const f32x4 q = {__int_as_float(__builtin_amdgcn_mov_dpp(b, 0x00, 0xf, 0xf, true)),   // quad_perm(0,0,0,0)
                    __int_as_float(__builtin_amdgcn_mov_dpp(b, 0x55, 0xf, 0xf, true)),   // (1,1,1,1)
                    __int_as_float(__builtin_amdgcn_mov_dpp(b, 0xAA, 0xf, 0xf, true)),   // (2,2,2,2)
                    __int_as_float(__builtin_amdgcn_mov_dpp(b, 0xFF, 0xf, 0xf, true))};  // (3,3,3,3)
   if ((threadIdx.x & 3) == 0) stc4(base, e * 4, q);
-#endif
 }
 // stc_quad's pre-split form (the persistent decoder's and the BiLSTM's split-f16 hand-offs): lanes
 // 4 q .. 4 q + 3 hold 4 consecutive k of one row; lane 4 q stores their f16 hi halves then their lo
@@ -186,11 +174,7 @@ __device__ __forceinline__ void gsync_arrive(unsigned* bar, unsigned& gen, unsig
   ++gen;
   if (threadIdx.x == 0) {
     const unsigned n = nwg ? nwg : gridDim.x;
-#ifdef TTS_BAR_NC8
-    const unsigned nc = 8u;  // A/B builds: one counter per XCD
-#else
     const unsigned nc = n >= 256 ? 16u : 8u;
-#endif
     unsigned* xc = bar + 64 + (blockIdx.x % nc) * 32;
     if (__hip_atomic_fetch_add(xc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (n / nc) * gen - 1)
       if (__hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nc * gen - 1)

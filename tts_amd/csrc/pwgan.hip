@@ -14,9 +14,9 @@
 // HBM per sample per block: x (+halo, L2) 256 B, c 320 B, skip r/w 512 B, x' 256 B.
 #include "common.h"
 #include "launch.h"
-
-#include <cstdlib>
 #include "split16.h"
+#include "switches.h"
+#include "x3_tile.h"
 
 namespace {
 constexpr int PW_TQ = 128;          // time columns per workgroup
@@ -509,8 +509,7 @@ __global__ __launch_bounds__(256 * WN) void pw_layer_x3_kernel(PwLayerArgs a, co
   };
 
   // weights: A fragments [m16 (8)][k-step][lane][hi 8 | lo 8]; sequence 0..8 = GEMM1, 9..10 = GEMM2
-  const __amdgpu_buffer_rsrc_t w1r = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(W1x), 0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t w2r = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(W2x), 0, 0x7fffffff, 0x00020000);
+  const __amdgpu_buffer_rsrc_t w1r = x3_rsrc(W1x), w2r = x3_rsrc(W2x);
   const int mt0 = wm * 2;
   constexpr int RSL = 3;  // weight ring slots
   constexpr int SD = 2;   // staging depth (k-steps ahead)
@@ -522,9 +521,7 @@ __global__ __launch_bounds__(256 * WN) void pw_layer_x3_kernel(PwLayerArgs a, co
     const int nk = g1 ? PX_NK1 : PX_NK2, ks = g1 ? seq : seq - PX_NK1;
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi) {
-      const int so = ((mt0 + mi) * nk + ks) * 2048;
-      r[mi][0] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(wr, lane * 32, so, 0));
-      r[mi][1] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(wr, lane * 32 + 16, so, 0));
+      x3_load_a(r[mi], wr, lane * 32, ((mt0 + mi) * nk + ks) * 2048);
     }
   };
 
@@ -673,45 +670,22 @@ __global__ __launch_bounds__(64 * NW, 1) void pw_layer_x3p_kernel(PwLayerArgs a,
   const int wm = wave;  // NW x 1 waves: 16 MI rows x 64 positions each
   const int nb = lane & 15, kg = 8 * (lane >> 4);
   bool bad = false;
-  if (wave == 0) {  // tiles per utterance, exclusive prefix sum
-    const int L = lane < B ? (a.lens[lane] + a.len_add) * a.hop : 0;
-    const int n = (L + TQ - 1) / TQ;
-    int v = n;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int y = __shfl_up(v, o, 64);
-      if (lane >= o) v += y;
-    }
-    tcum[lane] = v - n;
-    tlen[lane] = L;
-    if (lane == 63) tcum[64] = v;
-  }
+  // tiles per utterance (x3_tile.h): positions [q0, q0 + TQ) of utterance b's L samples
+  if (wave == 0) x3_tile_scan<TQ>(tcum, tlen, lane, lane < B ? (a.lens[lane] + a.len_add) * a.hop : 0);
   __syncthreads();
-  struct Tile {
-    int b, t0, T;
-  };
-  auto tile_of = [&](int i) {
-    const bool hit = lane < B && tcum[lane] <= i && i < tcum[lane + 1];
-    const unsigned long long m = __ballot(hit);
-    Tile r;
-    r.b = __builtin_amdgcn_readfirstlane(m ? __ffsll((long long)m) - 1 : 0);
-    r.t0 = __builtin_amdgcn_readfirstlane((i - tcum[r.b]) * TQ);
-    r.T = __builtin_amdgcn_readfirstlane(tlen[r.b]);
-    return r;
-  };
+  using Tile = X3Tile;
+  auto tile_of = [&](int i) { return x3_tile_of<TQ>(tcum, tlen, B, lane, i); };
 
   // GEMM1 weights [m16 (8)][k-step][lane][hi 8 | lo 8] in registers (this wave's m-tiles MI wm ..
   // MI wm + MI - 1); GEMM2's (32 KB) and the biases in LDS
   h8 w1[PX_NK1][MI][2];
   {
-    const __amdgpu_buffer_rsrc_t w1r = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(W1x), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t w1r = x3_rsrc(W1x);
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
       for (int ks = 0; ks < PX_NK1; ++ks) {
-        const int so = ((MI * wm + mi) * PX_NK1 + ks) * 2048;
-        w1[ks][mi][0] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(w1r, lane * 32, so, 0));
-        w1[ks][mi][1] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(w1r, lane * 32 + 16, so, 0));
+        x3_load_a(w1[ks][mi], w1r, lane * 32, ((MI * wm + mi) * PX_NK1 + ks) * 2048);
       }
     const h8* w2g = reinterpret_cast<const h8*>(W2x);
     for (int i = tid; i < 8 * PX_NK2 * 64 * 2; i += NTH) W2s[i] = w2g[i];
@@ -739,8 +713,8 @@ __global__ __launch_bounds__(64 * NW, 1) void pw_layer_x3p_kernel(PwLayerArgs a,
     const int cmax = xs ? PW_R : PW_A;
     const __amdgpu_buffer_rsrc_t r = xs ? rsrc_rows(a.x + (long)Tl.b * PW_R * a.Tmax, PW_R)
                                         : rsrc_rows(a.c + (long)Tl.b * PW_A * a.Tmax, PW_A);
-    const int t = Tl.t0 + sq + off;
-    const bool ok = t >= 0 && t < Tl.T && c0 < cmax;
+    const int t = Tl.q0 + sq + off;
+    const bool ok = t >= 0 && t < Tl.L && c0 < cmax;
     sok = ok ? (sok | (1u << ks)) : (sok & ~(1u << ks));
     const int vo = (min(c0, cmax - CPI) * a.Tmax + (ok ? t : 0)) * 4;
 #pragma unroll
@@ -780,7 +754,7 @@ __global__ __launch_bounds__(64 * NW, 1) void pw_layer_x3p_kernel(PwLayerArgs a,
         const int ch = wm * 16 * MI + mi * 16 + 4 * (lane >> 4) + j - (outw ? 0 : PW_R);
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) {
-          const int t = min(Tl.t0 + nb + ni * 16, Tl.T - 1);
+          const int t = min(Tl.q0 + nb + ni * 16, Tl.L - 1);
           res[mi][j][ni] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, (ch * a.Tmax + t) * 4, 0, 0));
         }
       }
@@ -875,8 +849,8 @@ __global__ __launch_bounds__(64 * NW, 1) void pw_layer_x3p_kernel(PwLayerArgs a,
           const int row = (outw ? R : R - PW_R) * a.Tmax;
 #pragma unroll
           for (int ni = 0; ni < 4; ++ni) {
-            const int tt = cur.t0 + nb + ni * 16;
-            if (tt >= cur.T) continue;
+            const int tt = cur.q0 + nb + ni * 16;
+            if (tt >= cur.L) continue;
             const float v = x3_value(am[mi][ni][j], ac[mi][ni][j]) + b2s[R];
             const float o = outw ? (v + res[mi][j][ni]) * 0.25f : (a.first ? v : res[mi][j][ni] + v);
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o), orr, (row + tt) * 4, 0, 0);
@@ -897,18 +871,13 @@ void launch_pw_layer_x3(const float* x, const float* c, float* xn, float* skip, 
                         int Tmax, int dil, int first, int B, unsigned* oflow, hipStream_t st) {
   TTS_CHECK(W1x && W2x && oflow, "pwgan split-f16: weights / range flag missing");
   PwLayerArgs a{x, c, xn, skip, nullptr, b1, nullptr, b2, lens, nullptr, len_add, hop, Tmax, dil, first};
-  static const int var = [] {
-    const char* e = std::getenv("TTS_PWGAN_TILE");
-    return e ? std::atoi(e) : 0;
-  }();
+  const int var = sw::pwgan_tile();
   // the persistent kernel addresses a row block of the (B, 80, Tmax) features with 32-bit buffer
   // offsets: utterances past 2^31 bytes per row block (~26 k frames at hop 256) take the per-tile
   // kernel, whose offsets are 64-bit
   const bool off32 = (long)PW_A * Tmax * 4 < (1L << 31);
   if (B <= 64 && h_lens && var != 1 && off32) {  // persistent, weights in registers (TTS_PWGAN_TILE=1: the per-tile kernel)
-    long ntiles = 0;
-    for (int b = 0; b < B; ++b) ntiles += ((long)(h_lens[b] + len_add) * hop + 63) / 64;
-    TTS_CHECK(ntiles < (1L << 30), "pwgan: too many tiles");
+    const long ntiles = x3_tile_count(h_lens, B, len_add, hop, 64, "pwgan");
     if (ntiles == 0) return;
     constexpr int lds = (PX_NK1 + 2) * 64 * PX_XR * 2 + 8 * PX_NK2 * 64 * 32;
     const int grid = (int)std::min<long>(ntiles, device_cu_count());

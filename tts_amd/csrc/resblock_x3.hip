@@ -21,9 +21,9 @@
 // Any operand outside the f16 range sets *oflow; the host then re-runs the call in fp32.
 #include "common.h"
 #include "split16.h"
+#include "x3_tile.h"
 
 #include <algorithm>
-#include <cstdlib>
 
 // bottleneck probes for tools/rbx3_bench.hip only (results are wrong in these builds):
 // RB_NO_WLOAD (the weight ring is loaded once and never refilled), RB_NO_LDS (MFMAs on register
@@ -46,16 +46,8 @@
 namespace {
 constexpr int X3_DMAX = 27;   // largest dilation (3^3, num_res_blocks <= 4)
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000);
-}
 __device__ __forceinline__ float lrelu_x3(float v) { return fmaxf(v, 0.2f * v); }  // == lrelu02
 }  // namespace
-
-// Tile of the persistent loop: utterance b, positions [q0, q0 + TQ) of its L = (lens + len_add) * mul
-struct RbTile {
-  int b, q0, L;
-};
 
 // CPB (round 6): channel chunks of 32 staged per barrier interval. The staging row holds CPB chunks
 // ([32 CPB hi | 32 CPB lo | 16 pad]: a stride of 8 mod 16 dwords, conflict-free as the 1-chunk row),
@@ -105,35 +97,13 @@ __global__ __launch_bounds__(64 * WM * WN) void resblock_x3_kernel(ResArgs a, in
   bool bad = false;   // staged inputs: ordered compare (catches NaN)
   float vmax = 0.f;   // h values: running max of |h| (split16.h absmax4)
 
-  // tile index -> (utterance, first position): per-utterance tile offsets (exclusive scan over the
-  // <= 64 lengths, once per workgroup, in LDS); a lookup is one LDS read per lane and a ballot
+  // tile index -> (utterance, first position): x3_tile.h
   __shared__ int tcum[65], tlen[64];
-  if (wave == 0) {
-    const int L = lane < a.B ? (a.lens[lane] + a.len_add) * a.mul : 0;
-    const int n = (L + TQ - 1) / TQ;
-    int v = n;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int y = __shfl_up(v, o, 64);
-      if (lane >= o) v += y;
-    }
-    tcum[lane] = v - n;
-    tlen[lane] = L;
-    if (lane == 63) tcum[64] = v;
-  }
+  if (wave == 0) x3_tile_scan<TQ>(tcum, tlen, lane, lane < a.B ? (a.lens[lane] + a.len_add) * a.mul : 0);
   lds_barrier();
   // the host's count may be an upper bound (lengths decoded on the device): the tiles that exist
   ntiles = min(ntiles, __builtin_amdgcn_readfirstlane(tcum[64]));
-  auto tile_of = [&](int i) {
-    const bool hit = lane < a.B && tcum[lane] <= i && i < tcum[lane + 1];
-    const unsigned long long m = __ballot(hit);
-    const int b = __builtin_amdgcn_readfirstlane(m ? __ffsll((long long)m) - 1 : 0);
-    RbTile r;
-    r.b = b;
-    r.q0 = __builtin_amdgcn_readfirstlane((i - tcum[b]) * TQ);
-    r.L = __builtin_amdgcn_readfirstlane(tlen[b]);
-    return r;
-  };
+  auto tile_of = [&](int i) { return x3_tile_of<TQ>(tcum, tlen, a.B, lane, i); };
 
   // ---- staging: item e = (channel octet g, row); rows fastest so that lanes read consecutive
   //      positions of one channel (coalesced); clamped addresses, no per-element guard
@@ -145,11 +115,11 @@ __global__ __launch_bounds__(64 * WM * WN) void resblock_x3_kernel(ResArgs a, in
     srow[j] = e - sg[j] * ROWS;
   }
   float st[2][SPT][8];
-  auto stage_load = [&](const RbTile& T, float (&sr)[SPT][8], int ch) {
+  auto stage_load = [&](const X3Tile& T, float (&sr)[SPT][8], int ch) {
 #ifdef RB_NO_XLOAD
     if (T.q0 + T.b + ch > 0 || blockIdx.x > 0) return;
 #endif
-    const __amdgpu_buffer_rsrc_t xr = rsrc(a.x + (long)T.b * a.sb);  // one utterance: < 2^31 bytes
+    const __amdgpu_buffer_rsrc_t xr = x3_rsrc(a.x + (long)T.b * a.sb);  // one utterance: < 2^31 bytes
     const int i0 = T.q0 - d;
     const bool interior = i0 >= 0 && i0 + ROWS <= T.L;
 #pragma unroll
@@ -208,7 +178,7 @@ __global__ __launch_bounds__(64 * WM * WN) void resblock_x3_kernel(ResArgs a, in
   //      sequence through a 3-slot ring that wraps into the next tile's phase 1, so every slot
   //      is reloaded in place right after its MFMAs and never waits at a tile boundary
   // buffer loads: the lane's 32 bytes are a VGPR offset, the (m-tile, k-step) block an SGPR one
-  const __amdgpu_buffer_rsrc_t wdr = rsrc(a.Wd16), wfr = rsrc(a.Wf16);
+  const __amdgpu_buffer_rsrc_t wdr = x3_rsrc(a.Wd16), wfr = x3_rsrc(a.Wf16);
   const int wlo = lane * 32;
   h8 ring[R][MI][2];
   auto wload = [&](h8 (&r)[MI][2], int seq) {
@@ -222,9 +192,7 @@ __global__ __launch_bounds__(64 * WM * WN) void resblock_x3_kernel(ResArgs a, in
     const int ks = p1 ? seq : seq - NK1;
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) {
-      const int so = ((mt0 + mi) * nk + ks) * 2048;
-      r[mi][0] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(wr, wlo, so, 0));
-      r[mi][1] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(wr, wlo + 16, so, 0));
+      x3_load_a(r[mi], wr, wlo, ((mt0 + mi) * nk + ks) * 2048);
     }
   };
 
@@ -232,7 +200,7 @@ __global__ __launch_bounds__(64 * WM * WN) void resblock_x3_kernel(ResArgs a, in
   // first tile's prologue; later tiles stage chunks 0 and 1 during the previous tile's phase 2.
   // Staging runs two chunks ahead: chunk c is loaded into register set c & 1 after chunk c - 3's
   // MFMAs and stored to LDS buffer c & 1 after chunk c - 1's.
-  RbTile cur = tile_of(t);
+  X3Tile cur = tile_of(t);
   stage_load(cur, st[0], 0);
 #pragma unroll
   for (int u = 0; u < R; ++u) wload(ring[u], u);
@@ -265,7 +233,7 @@ __global__ __launch_bounds__(64 * WM * WN) void resblock_x3_kernel(ResArgs a, in
     RB_STAMP(0);
     const int tn = t + gridDim.x;
     const bool more = tn < ntiles;
-    const RbTile nxt = more ? tile_of(tn) : cur;
+    const X3Tile nxt = more ? tile_of(tn) : cur;
     // the prefetch loads are issued unconditionally (a last tile re-loads itself): vmcnt is an
     // in-order counter, and a conditional load makes the compiler wait for everything (vmcnt(0))
     if (EARLY && NSC == 2) stage_load(nxt, st[0], 0);
@@ -397,9 +365,7 @@ static void launch_rbx3(const ResArgs& a, const int* h_lens, hipStream_t s) {
   ensure_dyn_lds((const void*)resblock_x3_kernel<C, TQ, WM, WN, R, CPB>, RB_DYN_LDS);
   const int ncu = device_cu_count();
   TTS_CHECK(lds <= RB_DYN_LDS, "resblock_x3: LDS tile too large");
-  long ntiles = 0;
-  for (int b = 0; b < a.B; ++b) ntiles += ((long)(h_lens[b] + a.len_add) * a.mul + TQ - 1) / TQ;
-  TTS_CHECK(ntiles < (1L << 30), "resblock_x3: too many tiles");
+  const long ntiles = x3_tile_count(h_lens, a.B, a.len_add, a.mul, TQ, "resblock_x3");
   if (ntiles == 0) return;
   const int grid = (int)std::min<long>(ntiles, ncu);
   const bool vec = a.Ls % 4 == 0 && a.sb % 4 == 0 && (reinterpret_cast<uintptr_t>(a.y) & 15) == 0;

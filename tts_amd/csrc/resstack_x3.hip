@@ -19,14 +19,12 @@
 // group j % WN.
 #include "common.h"
 #include "split16.h"
+#include "x3_tile.h"
 
 #include <algorithm>
 #include <type_traits>
 
 namespace {
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_s(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000);
-}
 __device__ __forceinline__ float lrelu_s(float v) { return fmaxf(v, 0.2f * v); }
 template <class T>
 __device__ __forceinline__ T pick3(T v0, T v1, T v2, int i) {  // wave-uniform select, no indexed kernarg
@@ -49,14 +47,6 @@ constexpr int ST_OFF = 16;  // halo rows per side (>= the sum of the fused dilat
   rs_trace[((long)blockIdx.x * RS_TRACE_TILES + it_) * 16 + (k)] = __builtin_amdgcn_s_memrealtime()
 #else
 #define RS_STAMP(k)
-#endif
-#ifndef RS_STAGE_AT
-#define RS_STAGE_AT 1
-#endif
-#ifdef RS_NO_SB
-#define RS_SB()
-#else
-#define RS_SB() __builtin_amdgcn_sched_barrier(0)
 #endif
 #ifdef RS_NO_MFMA
 #define RS_MMA(ah, al, bh, bl, am, ac) ((am)[0] += (float)(bh)[0] + (float)(bl)[7])
@@ -118,6 +108,8 @@ __global__ __launch_bounds__(64 * (C / 16) * WN) void resstack_x3_kernel(StackAr
   float vmax = 0.f;   // produced values: running max of |v| (split16.h absmax4)
   int t = blockIdx.x;
 
+  // x3_tile.h's x3_tile_scan, written out: called as the helper the same code schedules differently
+  // here, and the unfused C = 48 kernel then spills one more SGPR (profiles/r08/isa_diff.txt)
   if (wave == 0) {
     const int L = lane < a.B ? (a.lens[lane] + a.len_add) * a.mul : 0;
     const int n = (L + TQ - 1) / TQ;
@@ -145,19 +137,8 @@ __global__ __launch_bounds__(64 * (C / 16) * WN) void resstack_x3_kernel(StackAr
   lds_barrier();
   // the host's count may be an upper bound (lengths decoded on the device): the tiles that exist
   ntiles = min(ntiles, __builtin_amdgcn_readfirstlane(tcum[64]));
-  struct Tile {
-    int b, q0, L;
-  };
-  auto tile_of = [&](int i) {
-    const bool hit = lane < a.B && tcum[lane] <= i && i < tcum[lane + 1];
-    const unsigned long long m = __ballot(hit);
-    const int b = __builtin_amdgcn_readfirstlane(m ? __ffsll((long long)m) - 1 : 0);
-    Tile r;
-    r.b = b;
-    r.q0 = __builtin_amdgcn_readfirstlane((i - tcum[b]) * TQ);
-    r.L = __builtin_amdgcn_readfirstlane(tlen[b]);
-    return r;
-  };
+  using Tile = X3Tile;
+  auto tile_of = [&](int i) { return x3_tile_of<TQ>(tcum, tlen, a.B, lane, i); };
 
   // ---- staging of x_0: item = (channel octet, row), rows fastest (coalesced per channel)
   constexpr int SROWS = CTU ? CROWS : ROWS;
@@ -171,7 +152,7 @@ __global__ __launch_bounds__(64 * (C / 16) * WN) void resstack_x3_kernel(StackAr
   float st[SPT][8];
   // CTU: the ConvTranspose input of a tile, rows = input positions (q0 - OFF) / CTU - 1 + row
   auto stage_load_ct = [&](const Tile& T) {
-    const __amdgpu_buffer_rsrc_t xr = rsrc_s(a.xin + (long)T.b * a.sb_in);
+    const __amdgpu_buffer_rsrc_t xr = x3_rsrc(a.xin + (long)T.b * a.sb_in);
     constexpr int U = CTU ? CTU : 1;
     const int Lin = T.L / U, qb = (T.q0 - OFF) / U - 1;
 #pragma unroll
@@ -208,7 +189,7 @@ __global__ __launch_bounds__(64 * (C / 16) * WN) void resstack_x3_kernel(StackAr
     }
   };
   auto stage_load = [&](const Tile& T) {
-    const __amdgpu_buffer_rsrc_t xr = rsrc_s(a.x + (long)T.b * a.sb);
+    const __amdgpu_buffer_rsrc_t xr = x3_rsrc(a.x + (long)T.b * a.sb);
 #pragma unroll
     for (int j = 0; j < SPT; ++j) {
       int p = T.q0 - OFF + srow[j];
@@ -263,23 +244,18 @@ __global__ __launch_bounds__(64 * (C / 16) * WN) void resstack_x3_kernel(StackAr
   static_assert((SEQ0 + NB * NKB) % R == 0, "weight ring: a tile's weight sequence must be a multiple of R");
   auto wload = [&](h8 (&r)[2], int blk, int s) {  // s: k-step within block blk (compile-time)
     if (CTU && blk < 0) {
-      const __amdgpu_buffer_rsrc_t wr = rsrc_s(a.ct16);
+      const __amdgpu_buffer_rsrc_t wr = x3_rsrc(a.ct16);
       const int so = ((wave % CMT) * CKS + s) * 2048;
-      r[0] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(wr, wlo, so, 0));
-      r[1] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(wr, wlo + 16, so, 0));
+      x3_load_a(r, wr, wlo, so);
       return;
     }
     const bool p1 = s < NK1;
-    const __amdgpu_buffer_rsrc_t wr = rsrc_s(p1 ? pick3(a.wd16[0], a.wd16[1], a.wd16[2], blk) : pick3(a.wf16[0], a.wf16[1], a.wf16[2], blk));
+    const __amdgpu_buffer_rsrc_t wr = x3_rsrc(p1 ? pick3(a.wd16[0], a.wd16[1], a.wd16[2], blk) : pick3(a.wf16[0], a.wf16[1], a.wf16[2], blk));
     const int so = (wm * (p1 ? NK1 : NK2) + (p1 ? s : s - NK1)) * 2048;
-    r[0] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(wr, wlo, so, 0));
-    r[1] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(wr, wlo + 16, so, 0));
+    x3_load_a(r, wr, wlo, so);
   };
   // after k-step s of block blk: load the k-step R ahead (into the next block past its end)
   auto wnext = [&](h8 (&r)[2], int blk, int s) {
-#ifdef RS_NO_WLOAD
-    return;
-#endif
     const int nk = (CTU && blk < 0) ? CKS : NKB;
     if (s + R < nk) wload(r, blk, s + R);
     else wload(r, blk + 1 == NB ? (CTU ? -1 : 0) : blk + 1, s + R - nk);
@@ -309,11 +285,11 @@ __global__ __launch_bounds__(64 * (C / 16) * WN) void resstack_x3_kernel(StackAr
         bh[n] = RS_LD(p);
         bl[n] = RS_LD(p + CIN);
       }
-      RS_SB();
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int n = 0; n < NI; ++n) RS_MMA(ring[ks % R][0], ring[ks % R][1], bh[n], bl[n], am[n], ac[n]);
       wnext(ring[ks % R], -1, ks);
-      RS_SB();
+      __builtin_amdgcn_sched_barrier(0);
     }
     lds_barrier();  // the staged input (XL region) is dead from here
     const int m0 = mt * 16 + 4 * (lane >> 4), co0 = m0 / 2;  // rows m0 .. m0 + 3 = (co0, co0 + 1) x phases 0, 1
@@ -396,7 +372,7 @@ __global__ __launch_bounds__(64 * (C / 16) * WN) void resstack_x3_kernel(StackAr
         }
       }
       RS_STAMP(4 * bi + 1);
-      if (RS_STAGE_AT == 1 && last) load_tile(nxt);
+      if (last) load_tile(nxt);
       // ---------------- phase 1: h = Wd . lrelu(x_k) ----------------
 #pragma unroll
       for (int ni = 0; ni < NI; ++ni) am[ni] = ac[ni] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -422,12 +398,12 @@ __global__ __launch_bounds__(64 * (C / 16) * WN) void resstack_x3_kernel(StackAr
           bh[ni] = RS_LD(p);
           bl[ni] = RS_LD(p + C);
         }
-        RS_SB();
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni)
           RS_MMA(ring[(g0 + s) % R][0], ring[(g0 + s) % R][1], bh[ni], bl[ni], am[ni], ac[ni]);
         wnext(ring[(g0 + s) % R], bi, s);
-        RS_SB();
+        __builtin_amdgcn_sched_barrier(0);
       }
       // lrelu(h + b_d) into HX's h columns; rows outside [vlo, vhi) as zeros
       {
@@ -449,7 +425,6 @@ __global__ __launch_bounds__(64 * (C / 16) * WN) void resstack_x3_kernel(StackAr
       }
       lds_barrier();
       RS_STAMP(4 * bi + 2);
-      if (RS_STAGE_AT == 0 && last) load_tile(nxt);  // in flight during the last phase 2 and the stores
       // ---------------- phase 2: y = [W1 | Wsc] . [lrelu(h); x_k] ----------------
 #pragma unroll
       for (int kc = 0; kc < NK2; ++kc) {
@@ -463,7 +438,7 @@ __global__ __launch_bounds__(64 * (C / 16) * WN) void resstack_x3_kernel(StackAr
             bl[ni] = RS_LD(p + 2 * C);
           }
         }
-        RS_SB();
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni)
           if (last)  // transposed (D = HX^T . Wf^T): the stores below write 4 positions of one channel
@@ -471,11 +446,10 @@ __global__ __launch_bounds__(64 * (C / 16) * WN) void resstack_x3_kernel(StackAr
           else
             RS_MMA(ring[(g0 + s) % R][0], ring[(g0 + s) % R][1], bh[ni], bl[ni], am[ni], ac[ni]);
         wnext(ring[(g0 + s) % R], bi, s);
-        RS_SB();
+        __builtin_amdgcn_sched_barrier(0);
       }
       const f32x4 bf = *reinterpret_cast<const f32x4*>(bias[bi][1] + co);
       RS_STAMP(4 * bi + 3);
-      if (RS_STAGE_AT == 2 && last) load_tile(nxt);
       if (!last) {
         lds_barrier();  // every wave is done reading x_k
 #pragma unroll
@@ -548,9 +522,7 @@ static void launch_rsx3(const StackArgs& a, const int* h_lens, hipStream_t s) {
   static_assert(lds + 3 * 2 * C * 4 + 65 * 4 + 64 * 4 <= 160 * 1024, "LDS");
   ensure_dyn_lds((const void*)resstack_x3_kernel<C, TQ, WN, NI, CTU>, (int)lds);
   const int ncu = device_cu_count();
-  long ntiles = 0;
-  for (int b = 0; b < a.B; ++b) ntiles += ((long)(h_lens[b] + a.len_add) * a.mul + TQ - 1) / TQ;
-  TTS_CHECK(ntiles < (1L << 30), "resstack_x3: too many tiles");
+  const long ntiles = x3_tile_count(h_lens, a.B, a.len_add, a.mul, TQ, "resstack_x3");
   if (ntiles == 0) return;
   const int grid = (int)std::min<long>(ntiles, ncu);
   resstack_x3_kernel<C, TQ, WN, NI, CTU><<<grid, 64 * (C / 16) * WN, lds, s>>>(a, (int)ntiles);

@@ -161,10 +161,6 @@ __device__ __forceinline__ float absmax4(float mx, const f32x4& v) {
 // of 8 consecutive rows from 2-way to conflict-free. Every access of a tile's halves goes through
 // it; offsets that are multiples of 16 halves (C, 2C, 32 ch) commute with the XOR.
 __device__ __forceinline__ int lds_rsw(int r) {
-#ifdef TTS_NO_LDS_SWZ  // A/B builds: the unswizzled layout
-  return 0 * r;
-#else
   return ((r >> 2) & 1) << 3;
-#endif
 }
 #endif
