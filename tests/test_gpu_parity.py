@@ -1104,6 +1104,25 @@ def test_decoder_barrier_block_calibration_bit_identical(tmp_path):
         assert np.array_equal(outs[0][k], outs[1][k]), k
 
 
+@pytest.mark.gpu
+def test_tacotron2_graph_decoder_matches_reference(taco_sig, tmp_path):
+    """The captured-graph decoder (decoder.hip's per-step kernels replayed as CHUNK-step graphs: the
+    path of TTS_DECODER=graph and of any device that is not a 256-CU part) against the reference
+    fixture, at the persistent path's tolerances: the three r = 2 utterances of
+    test_tacotron2_batched_matches_reference, run in a child process (the switch is read once per
+    process) through tools/taco_dump.py's golden mode."""
+    import subprocess
+    import sys
+    path = str(tmp_path / "graph.npz")
+    env = dict(os.environ, TTS_DECODER="graph")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "taco_dump.py"), path, "golden"], env=env,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    o = np.load(path)
+    assert int(o["path"]) == 0, "the decode did not take the captured-graph path"
+    _check_taco(taco_sig, 2, o["dec"], o["post"], o["align"], o["stop"], o["steps"], range(3))
+
+
 # --------------------------------------------------------------------- GE2E speaker encoder
 @pytest.mark.parametrize("tag,proj", [("proj", True), ("noproj", False)])
 def test_ge2e_speaker_encoder_matches_reference(tag, proj):

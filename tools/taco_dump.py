@@ -4,6 +4,11 @@ separate processes (e.g. TTS_BAR_CALIBRATE=0 / 1: the decoder's barrier blocks p
 taken in order; the barrier's place must not change a single bit).
 
     python tools/taco_dump.py out.npz [n]     (n utterances, default 12; > 32 repeats the profile)
+    python tools/taco_dump.py out.npz golden  (the taco_sigmoid fixture's three r = 2 utterances, built
+                                               as tests/test_gpu_parity.py's batched test builds them)
+
+Every file also holds `path`, the decoder path of the call (Engine.decoder_stats(): 1 persistent,
+0 captured step graphs).
 """
 import os
 import sys
@@ -13,23 +18,45 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-import bench  # noqa: E402
-from tts_amd.workload import forced_steps, lj_profile, pad_batch, synthetic_ids  # noqa: E402
+from tts_amd._lib import get_engine  # noqa: E402
 
 
-def main(path, n=12):
-    dev = torch.device("cuda", 0)
+def bench_run(dev, n):
+    import bench
+    from tts_amd.workload import forced_steps, lj_profile, pad_batch, synthetic_ids
     taco, _, _, _, _, _ = bench.build_models(dev)
     taco.decoder.verbose = False
     taco.decoder.set_r(2)
     T, M = lj_profile()
     T, M = (list(T) * 2)[:n], (list(M) * 2)[:n]
     batch, lens = pad_batch(synthetic_ids(T))
-    dec, post, align, stop = taco.inference(torch.from_numpy(batch).to(dev), text_lengths=lens,
-                                            max_decoder_steps=forced_steps(M, 2))
+    return taco, taco.inference(torch.from_numpy(batch).to(dev), text_lengths=lens,
+                                max_decoder_steps=forced_steps(M, 2))
+
+
+def golden_run(dev, r=2):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from helpers import build_taco, load_fixture, taco_state_dict
+    fx = load_fixture("taco_sigmoid")
+    cfg, sd = taco_state_dict(fx, r=r)
+    m = build_taco(cfg, sd, dev)
+    m.decoder.set_r(r)
+    m.decoder.max_decoder_steps = int(fx[f"r{r}_max_steps"])
+    ids = [fx[f"r{r}_u{i}_ids"] for i in range(3)]
+    T = max(len(x) for x in ids)
+    batch = np.zeros((3, T), np.int64)
+    for i, x in enumerate(ids):
+        batch[i, :len(x)] = x
+    return m, m.inference(torch.from_numpy(batch).to(dev), text_lengths=[len(x) for x in ids])
+
+
+def main(path, mode="12"):
+    dev = torch.device("cuda", 0)
+    taco, (dec, post, align, stop) = golden_run(dev) if mode == "golden" else bench_run(dev, int(mode))
     np.savez(path, dec=dec.cpu().numpy(), post=post.cpu().numpy(), align=align.cpu().numpy(),
-             stop=stop.cpu().numpy(), steps=np.asarray(taco.last_steps))
+             stop=stop.cpu().numpy(), steps=np.asarray(taco.last_steps),
+             path=np.asarray(get_engine("cuda:0").decoder_stats()[0]))
 
 
 if __name__ == "__main__":
-    main(sys.argv[1], int(sys.argv[2]) if len(sys.argv) > 2 else 12)
+    main(*sys.argv[1:3])

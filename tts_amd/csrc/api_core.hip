@@ -280,8 +280,8 @@ int tts_ctx_create(int device, tts_ctx** out) {
     for (auto& e : c->ev_dec) HIP_OK(hipEventCreate(&e));
     HIP_OK(hipEventCreateWithFlags(&c->ev_status, hipEventDisableTiming));
     for (auto& t : c->vt) HIP_OK(hipEventCreateWithFlags(&t.ev, hipEventDisableTiming));
-    HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&c->pinned), 1024, hipHostMallocDefault));
-    std::memset(c->pinned, 0, 1024);
+    HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&c->pinned), PIN_N * 4, hipHostMallocDefault));
+    std::memset(c->pinned, 0, PIN_N * 4);
     *out = c.release();
   });
 }

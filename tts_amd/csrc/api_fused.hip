@@ -116,7 +116,7 @@ int64_t taco_mbmelgan_submit(tts_ctx* c, const int64_t* d_ids, const int32_t* h_
     throw;
   }
   c->in_submit = false;
-  const bool taco_oflow = c->gemm_x3 && c->flag_read && c->pinned[12];
+  const bool taco_oflow = c->gemm_x3 && c->flag_read && c->pinned[PIN_FLAG];
   c->flag_read = false;
   int S = 0;
   for (int b = 0; b < B; ++b) S = std::max(S, (int)h_steps[b]);

@@ -13,15 +13,17 @@ using namespace ttsh;
 
 namespace {
 
+DecCtlBlock* ctl_block(const TacoWS& W) { return static_cast<DecCtlBlock*>(W.ctl.p); }
+
 DecDev make_dev(tts_ctx* c, int Bact) {
   auto& W = c->tws;
   DecDev d{};
-  int* ci = W.ctl.i();
-  d.ctl = reinterpret_cast<DecCtl*>(ci);
-  d.done = ci + 4;
-  d.steps = ci + 4 + BMAX;
-  d.status = ci + 4 + 2 * BMAX;
-  d.max_steps = ci + 4 + 3 * BMAX;
+  DecCtlBlock* cb = ctl_block(W);
+  d.ctl = &cb->ctl;
+  d.done = cb->done;
+  d.steps = cb->steps;
+  d.status = cb->status;
+  d.max_steps = cb->max_steps;
   d.lens = W.lens.i();
   d.dec_out = W.dec.f();
   d.align_out = W.align.f();
@@ -41,12 +43,6 @@ SkSeg seg(const float* base, int Ktot, int k0, int K) {
   return s;
 }
 
-SkJob job0() {
-  SkJob j;
-  std::memset(&j, 0, sizeof(j));
-  return j;
-}
-
 // the 5 launches of decoder step j of a chunk (parity j & 1 selects the h_dec buffer) over the
 // first MT batch tiles (rows >= 16*MT must all be finished)
 void enqueue_step(tts_ctx* c, int j, int which_only, hipStream_t s, int MT) {
@@ -60,13 +56,13 @@ void enqueue_step(tts_ctx* c, int j, int which_only, hipStream_t s, int MT) {
     SkArgs a{};
     a.njobs = 2;
     a.MT = MT;
-    SkJob& J = a.job[0] = job0();  // layer 1 (result kept in LDS)
+    SkJob& J = a.job[0];  // layer 1 (result kept in LDS)
     J.seg[0] = seg(W.y.f(), YLD, 80 * (r - 1), 80);
     J.nseg = 1;
     J.K = 80;
     J.W = M.pre1.f();
     J.ntiles = 16;
-    SkJob& J2 = a.job[1] = job0();  // layer 2
+    SkJob& J2 = a.job[1];  // layer 2
     J2.K = 256;
     J2.W = M.pre2.f();
     J2.ntiles = 16;
@@ -82,7 +78,7 @@ void enqueue_step(tts_ctx* c, int j, int which_only, hipStream_t s, int MT) {
     SkArgs a{};
     a.njobs = 1;
     a.MT = MT;
-    SkJob& J = a.job[0] = job0();
+    SkJob& J = a.job[0];
     J.seg[0] = seg(W.pb.f(), 256, 0, 256);
     J.nseg = 1;
     J.K = 256;
@@ -126,7 +122,7 @@ void enqueue_step(tts_ctx* c, int j, int which_only, hipStream_t s, int MT) {
     SkArgs a{};
     a.njobs = 1;
     a.MT = MT;
-    SkJob& J = a.job[0] = job0();
+    SkJob& J = a.job[0];
     J.seg[0] = seg(W.hatt.f(), 1024, 0, 1024);
     J.seg[1] = seg(W.ctx.f(), 512, 0, 512);
     J.seg[2] = seg(hd_cur, 1024, 0, 1024);
@@ -145,7 +141,7 @@ void enqueue_step(tts_ctx* c, int j, int which_only, hipStream_t s, int MT) {
     SkArgs a{};
     a.njobs = 2;
     a.MT = MT;
-    SkJob& J = a.job[0] = job0();
+    SkJob& J = a.job[0];
     J.seg[0] = seg(hd_nxt, 1024, 0, 1024);
     J.seg[1] = seg(W.ctx.f(), 512, 0, 512);
     J.nseg = 2;
@@ -160,7 +156,7 @@ void enqueue_step(tts_ctx* c, int j, int which_only, hipStream_t s, int MT) {
     J.frames_r = r;
     J.lead_stop = 1;
     J.stop_part = W.spart.f();
-    SkJob& J2 = a.job[1] = job0();  // (+ biases)
+    SkJob& J2 = a.job[1];  // (+ biases)
     J2.seg[0] = seg(W.ctx.f(), 512, 0, 512);
     J2.seg[1] = seg(W.hatt.f(), 1024, 0, 1024);
     J2.nseg = 2;
@@ -274,15 +270,21 @@ void run_encoder(tts_ctx* c, const int64_t* ids, int B, int T_max, float* enc_ou
 // a persistent BiLSTM whose grid barrier timed out set its error word. The words are read on the
 // library stream (ordered after the BiLSTM launch and its arm fill; c->s is non-blocking, so a
 // null-stream copy would not be), then the stream is drained before they are looked at.
+constexpr const char* ENC_BAR_MSG =
+    "persistent BiLSTM: grid barrier timed out (workgroups not co-resident) or preempted past "
+    "TTS_BARRIER_TIMEOUT_MS; retrying the call is safe)";
+bool all_zero(const int* p, int n) {
+  return std::all_of(p, p + n, [](int w) { return w == 0; });
+}
 void check_encoder_barrier(tts_ctx* c) {
   if (!c->tws.enc_persist) return;
-  int* pw = c->pinned + 240;  // one error word per recurrence (2 directions x up to 2 row groups)
+  int* pw = c->pinned + PIN_ENC;  // one error word per recurrence (2 directions x up to 2 row groups)
   const int nd = std::min(c->tws.enc_ndom, ENC_NDOM_MAX);
-  pw[0] = pw[1] = pw[2] = pw[3] = 0;
+  std::fill(pw, pw + ENC_NDOM_MAX, 0);
   const unsigned* words = reinterpret_cast<const unsigned*>(c->tws.lc.p);
   for (int i = 0; i < nd; ++i) HIP_OK(hipMemcpyAsync(&pw[i], words + i * BAR_WORDS + 16, 4, hipMemcpyDeviceToHost, c->s));
   HIP_OK(hipStreamSynchronize(c->s));
-  TTS_CHECK(pw[0] == 0 && pw[1] == 0 && pw[2] == 0 && pw[3] == 0, "persistent BiLSTM: grid barrier timed out (workgroups not co-resident) or preempted past TTS_BARRIER_TIMEOUT_MS; retrying the call is safe)");
+  TTS_CHECK(all_zero(pw, ENC_NDOM_MAX), ENC_BAR_MSG);
 }
 
 void run_postnet(tts_ctx* c, const float* dec, long dec_b, const int* mlens, int B, int Mmax_alloc, int max_q,
@@ -362,16 +364,17 @@ void gather4_rows(const Gather4& g, const int* d_map, int B, hipStream_t s) {
 
 // Per-call host arguments as kernel arguments (one launch instead of three pageable uploads):
 // decode order and its inverse, lengths in decode order, and the decoder control block
-// [base, all_done, active_tiles, pad | done | steps | status | max_steps] (DecCtl + BMAX each)
+// (DecCtlBlock: base = 0, all_done = 0, active_tiles = MT, done / steps / status = 0, max_steps)
 struct TacoSetup {
   int B, MT;
   int perm[BMAX], inv[BMAX], lens[BMAX], max_steps[BMAX];
 };
-__global__ void taco_setup_kernel(TacoSetup a, int* map, int* lens, int* ctl, unsigned* zero_flag) {
+__global__ void taco_setup_kernel(TacoSetup a, int* map, int* lens, DecCtlBlock* cb, unsigned* zero_flag) {
   if (zero_flag && threadIdx.x == 0) *zero_flag = 0u;  // a fused call's range flag (no separate fill)
-  for (int e = threadIdx.x; e < 4 + 4 * BMAX; e += blockDim.x) {
-    const int ms = e - 4 - 3 * BMAX;
-    ctl[e] = e == 2 ? a.MT : (ms >= 0 && ms < a.B ? a.max_steps[ms] : 0);
+  if (threadIdx.x == 0) cb->ctl = DecCtl{0, 0, a.MT, 0};
+  for (int b = threadIdx.x; b < BMAX; b += blockDim.x) {
+    cb->done[b] = cb->steps[b] = cb->status[b] = 0;
+    cb->max_steps[b] = b < a.B ? a.max_steps[b] : 0;
   }
   const int i = threadIdx.x;
   if (i < a.B) {
@@ -411,9 +414,9 @@ __global__ void taco_state_kernel(const float* hatt, const float* catt, const fl
 }
 
 // decode-order mel lengths for the postnet (steps * r), from the decoder results on the device
-__global__ void taco_mlens_kernel(const int* ctl, int B, int r, int* mlens) {
+__global__ void taco_mlens_kernel(const DecCtlBlock* cb, int B, int r, int* mlens) {
   const int i = threadIdx.x;
-  if (i < B) mlens[i] = ctl[4 + BMAX + i] * r;
+  if (i < B) mlens[i] = cb->steps[i] * r;
 }
 
 // gather every status word the host checks after a Tacotron2 call into one block (TS_* layout)
@@ -423,12 +426,12 @@ struct DecSlots {
 // A fused call (vlens set) also writes the vocoder's mel lengths in caller order, steps * r of
 // decode row inv[b], raised to Lmin where shorter (TS_VERR: the call fails)
 __global__ void taco_status_kernel(const unsigned* enc_bar, int nenc, const unsigned* dec_bar, DecSlots dslot, int ndec,
-                                   const int* ctl, const unsigned* flag, int* st, int B, const int* inv, int r,
-                                   int Lmin, int* vlens) {
+                                   const DecCtlBlock* cb, const unsigned* flag, int* st, int B, const int* inv,
+                                   int r, int Lmin, int* vlens) {
   const int i = threadIdx.x;
   int short_row = 0;
   if (vlens && i < B) {
-    int L = ctl[4 + BMAX + inv[i]] * r;
+    int L = cb->steps[inv[i]] * r;
     if (L < Lmin) {
       short_row = 1;
       L = Lmin;
@@ -437,7 +440,8 @@ __global__ void taco_status_kernel(const unsigned* enc_bar, int nenc, const unsi
   }
   short_row = __syncthreads_or(short_row);
   if (i == 0) st[TS_VERR] = short_row;
-  if (i < 3 * BMAX) st[TS_RES + i] = ctl[4 + i];
+  const int* res = cb->done;  // done | steps | status, contiguous (decoder.h)
+  if (i < 3 * BMAX) st[TS_RES + i] = res[i];
   if (i < ENC_NDOM_MAX) st[TS_ENC + i] = enc_bar && i < nenc ? (int)enc_bar[i * BAR_WORDS + 16] : 0;
   if (i < PMAX_LAUNCH) {
     st[TS_DEC + i] = dec_bar && i < ndec ? (int)dec_bar[dslot.v[i] * BAR_WORDS + 16] : 0;
@@ -453,7 +457,7 @@ hipGraphExec_t step_graph(tts_ctx* c, int MT, hipStream_t s) {
   HIP_OK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
   try {
     for (int j = 0; j < CHUNK; ++j) enqueue_step(c, j, -1, s, MT);
-    launch_dec_advance(reinterpret_cast<DecCtl*>(W.ctl.p), CHUNK, s);
+    launch_dec_advance(&ctl_block(W)->ctl, CHUNK, s);
   } catch (...) {
     hipGraph_t tmp;
     (void)hipStreamEndCapture(s, &tmp);
@@ -470,11 +474,10 @@ bool use_persistent(tts_ctx* c) {
   return c->tws.MT <= PMAX_LAUNCH && persist_supported(c->device);
 }
 
-// the whole decode as one cooperative launch per batch-tile count (decoder_persist.hip)
-void run_persistent(tts_ctx* c, int r, float thr, hipStream_t s) {
+// the persistent decoder's arguments: weights, workspace and per-call scalars (no stream work)
+PArgs persist_args(tts_ctx* c, int r, float thr) {
   auto& M = c->taco;
   auto& W = c->tws;
-  build_pj(c, r);
   PArgs a{};
   a.dec_w = M.dec_w.f();
   a.dec_b = M.dec_bias.f();
@@ -491,33 +494,17 @@ void run_persistent(tts_ctx* c, int r, float thr, hipStream_t s) {
   a.pj_x3 = dx3 ? M.pj_x3.h() : nullptr;
   a.pj_w = M.pj_w.f();
   a.pj_b = M.pj_b.f();
-  {  // per-row biases: projection (always), speaker columns when the model has them
-    const int YP = (1 + 5 * r + 16) * 16;
-    const int N = M.spk_dim ? 8320 + YP : YP;
-    const int pj0 = M.spk_dim ? 8320 : 0;
-    const int Bp = W.MT * 16;
-    grow<float>(W.spkb, (size_t)64 * (8320 + 112 * 16), W.gen);
-    TTS_CHECK(W.B <= SPK_BMAX || !M.spk_dim, "multi-speaker decoding: at most 64 utterances per call");
-    const int Bs = M.spk_dim ? W.B : 0;
-    TTS_CHECK(M.spk_dim <= 512, "speaker vectors of at most 512 dims");
-    // Graves with speakers: the projection columns hold W_s s alone; the kernel adds the bias and
-    // scales W_s s by the step's sum of attention weights (PArgs::spk_scale)
-    a.spk_scale = M.graves && M.spk_dim ? 1 : 0;
-    {
-      const float* wt = M.spk_dim ? M.spk_wT.f() : nullptr;
-      const int es = M.spk_dim, p0 = a.spk_scale ? N : pj0;
-      const dim3 g((N + 63) / 64);
-      if (Bs <= 16) spk_bias_kernel<16><<<g, 256, 0, s>>>(W.spk.f(), Bs, es, wt, N, M.pj_b.f(), p0, Bp, W.spkb.f());
-      else if (Bs <= 32) spk_bias_kernel<32><<<g, 256, 0, s>>>(W.spk.f(), Bs, es, wt, N, M.pj_b.f(), p0, Bp, W.spkb.f());
-      else spk_bias_kernel<64><<<g, 256, 0, s>>>(W.spk.f(), Bs, es, wt, N, M.pj_b.f(), p0, Bp, W.spkb.f());
-    }
-    HIP_OK(hipGetLastError());
-    a.spk_ld = N;
-    a.pjb_rows = W.spkb.f() + pj0;
-    a.spk_att = M.spk_dim ? W.spkb.f() : nullptr;
-    a.spk_dec = M.spk_dim ? W.spkb.f() + 4096 : nullptr;
-    a.spk_penc = M.spk_dim ? W.spkb.f() + 8192 : nullptr;
-  }
+  // per-row biases in W.spkb (stage_row_biases): the projection's (always) behind the speaker
+  // columns, which exist when the model has speakers
+  const int YP = (1 + 5 * r + 16) * 16, pj0 = M.spk_dim ? 8320 : 0;
+  a.spk_ld = pj0 + YP;
+  // Graves with speakers: the projection columns hold W_s s alone; the kernel adds the bias and
+  // scales W_s s by the step's sum of attention weights
+  a.spk_scale = M.graves && M.spk_dim ? 1 : 0;
+  a.pjb_rows = W.spkb.f() + pj0;
+  a.spk_att = M.spk_dim ? W.spkb.f() : nullptr;
+  a.spk_dec = M.spk_dim ? W.spkb.f() + 4096 : nullptr;
+  a.spk_penc = M.spk_dim ? W.spkb.f() + 8192 : nullptr;
   // decoder variants
   a.pre1_b0 = M.prenet_bn ? M.pre1_b0.f() : nullptr;
   a.pre2_b = M.prenet_bn ? M.pre2_b.f() : nullptr;
@@ -530,7 +517,6 @@ void run_persistent(tts_ctx* c, int r, float thr, hipStream_t s) {
   a.win_idx = W.win_idx.i();
   a.fwd_u = W.fwd_u.f();
   a.part_f = W.apf.f();
-  if (M.windowing) HIP_OK(hipMemsetAsync(W.win_idx.p, 0xff, 64 * 4, s));  // -1: before the first step
   a.gK = M.graves ? M.graves_K : 0;
   a.na1_w = M.na1_w.f();
   a.na1_b = M.na1_b.f();
@@ -538,11 +524,6 @@ void run_persistent(tts_ctx* c, int r, float thr, hipStream_t s) {
   a.na2_b = M.na2_b.f();
   a.gh = W.gh.f();
   a.gmu = W.gmu.f();
-  if (M.graves) HIP_OK(hipMemsetAsync(W.gmu.p, 0, 64 * 16 * 4, s));  // mu_prev = 0 (common_layers.py:143)
-  if (M.forward_attn) {
-    static const std::vector<float> half(64, 0.5f);  // u = 0.5 (common_layers.py:241)
-    HIP_OK(hipMemcpyAsync(W.fwd_u.p, half.data(), 64 * 4, hipMemcpyHostToDevice, s));
-  }
   a.pre2_w = M.pre2.f();
   a.WqT = M.WqT.f();
   a.Wcomb = M.Wcomb.f();
@@ -576,73 +557,119 @@ void run_persistent(tts_ctx* c, int r, float thr, hipStream_t s) {
   a.softmax = M.softmax;
   a.thr = thr;
   a.bar = reinterpret_cast<unsigned*>(W.pbar.p);
+  return a;
+}
+
+// the per-row biases the kernel reads through a.pjb_rows / a.spk_*: projection columns (always),
+// speaker columns when the model has them
+void stage_row_biases(tts_ctx* c, const PArgs& a, hipStream_t s) {
+  auto& M = c->taco;
+  auto& W = c->tws;
+  const int N = a.spk_ld, pj0 = (int)(a.pjb_rows - W.spkb.f()), Bp = W.MT * 16;
+  TTS_CHECK(W.B <= SPK_BMAX || !M.spk_dim, "multi-speaker decoding: at most 64 utterances per call");
+  const int Bs = M.spk_dim ? W.B : 0;
+  TTS_CHECK(M.spk_dim <= 512, "speaker vectors of at most 512 dims");
+  const float* wt = M.spk_dim ? M.spk_wT.f() : nullptr;
+  const int es = M.spk_dim, p0 = a.spk_scale ? N : pj0;
+  const dim3 g((N + 63) / 64);
+  if (Bs <= 16) spk_bias_kernel<16><<<g, 256, 0, s>>>(W.spk.f(), Bs, es, wt, N, M.pj_b.f(), p0, Bp, W.spkb.f());
+  else if (Bs <= 32) spk_bias_kernel<32><<<g, 256, 0, s>>>(W.spk.f(), Bs, es, wt, N, M.pj_b.f(), p0, Bp, W.spkb.f());
+  else spk_bias_kernel<64><<<g, 256, 0, s>>>(W.spk.f(), Bs, es, wt, N, M.pj_b.f(), p0, Bp, W.spkb.f());
+  HIP_OK(hipGetLastError());
+}
+
+// state the decoder variants carry across steps, at its value before the first step
+void reset_variant_state(tts_ctx* c, hipStream_t s) {
+  auto& M = c->taco;
+  auto& W = c->tws;
+  if (M.windowing) HIP_OK(hipMemsetAsync(W.win_idx.p, 0xff, 64 * 4, s));  // -1: before the first step
+  if (M.graves) HIP_OK(hipMemsetAsync(W.gmu.p, 0, 64 * 16 * 4, s));  // mu_prev = 0 (common_layers.py:143)
+  if (M.forward_attn) {
+    static const std::vector<float> half(64, 0.5f);  // u = 0.5 (common_layers.py:241)
+    HIP_OK(hipMemcpyAsync(W.fwd_u.p, half.data(), 64 * 4, hipMemcpyHostToDevice, s));
+  }
+}
+
+constexpr size_t PTRACE_WORDS = (size_t)8 * 24 * 256;
+// TTS_PTRACE=<file>: the traced launch's phase timestamps, written out once it has run
+void dump_ptrace(const char* file, const DevBuf& buf, hipStream_t s) {
+  HIP_OK(hipStreamSynchronize(s));
+  std::vector<unsigned long long> h(PTRACE_WORDS);
+  HIP_OK(hipMemcpy(h.data(), buf.p, h.size() * 8, hipMemcpyDeviceToHost));
+  if (FILE* fp = std::fopen(file, "wb")) {
+    std::fwrite(h.data(), 8, h.size(), fp);
+    std::fclose(fp);
+  }
+}
+
+// TTS_DIAG_XCC: print each launch's workgroup -> XCD map and the hand-off addresses
+void print_xdiag(tts_ctx* c, const PArgs& a, hipStream_t s) {
+  auto& W = c->tws;
+  HIP_OK(hipStreamSynchronize(s));
+  std::vector<unsigned> h((size_t)PMAX_LAUNCH * 256);
+  HIP_OK(hipMemcpy(h.data(), W.xdiag.p, h.size() * 4, hipMemcpyDeviceToHost));
+  for (int li = 0; li < c->dec_nlaunch; ++li) {
+    std::fprintf(stderr, "TTS_DIAG_XCC launch %d: wg0 xcc %u, wg0..15:", li, h[li * 256]);
+    for (int k = 0; k < 16; ++k) std::fprintf(stderr, " %u", h[li * 256 + k]);
+    std::fprintf(stderr, "\n");
+  }
+  std::fprintf(stderr, "TTS_DIAG_XCC addresses: bar %p pq %p hatt %p ctx %p hdec0 %p pb %p\n", (void*)W.pbar.p,
+               (void*)a.pq, (void*)a.hatt, (void*)a.ctx, (void*)a.hdec0, (void*)a.pb);
+}
+
+// one cooperative launch per batch-tile count, MT down to 1; each launch takes over where the last
+// one's trailing tile finished
+void launch_cascade(tts_ctx* c, PArgs a, hipStream_t s) {
+  auto& W = c->tws;
   // TTS_PTRACE=<file>: phase timestamps of 8 steps from step TTS_PTRACE_T0 (default 100)
-  DevBuf& trace_buf = W.trace;
   const char* tr = sw::ptrace_file();
   TTS_CHECK(!tr || persist_trace_built(), "TTS_PTRACE needs a library built with -DTTS_PHASE_TRACE "
                                           "(tools/build_variants.sh trace -DTTS_PHASE_TRACE; TTSHIP_LIB=tools/var/lib_trace.so)");
+  unsigned long long* trace_p = nullptr;
   if (tr) {
-    trace_buf.ensure((size_t)8 * 24 * 256 * 8);
-    HIP_OK(hipMemsetAsync(trace_buf.p, 0, (size_t)8 * 24 * 256 * 8, s));
-    a.trace = static_cast<unsigned long long*>(trace_buf.p);
-    a.atrace = a.trace + (size_t)8 * 16 * 256;
+    W.trace.ensure(PTRACE_WORDS * 8);
+    HIP_OK(hipMemsetAsync(W.trace.p, 0, PTRACE_WORDS * 8, s));
+    trace_p = static_cast<unsigned long long*>(W.trace.p);
     a.trace_t0 = sw::ptrace_t0();
   }
   const int trace_li = sw::ptrace_launch();
-  unsigned long long* const trace_p = a.trace;
-  unsigned long long* const atrace_p = a.atrace;
   const bool xdiag = sw::diag_xcc();
-  DevBuf& xdiag_buf = W.xdiag;
-  if (xdiag) xdiag_buf.ensure((size_t)PMAX_LAUNCH * 256 * 4);
+  if (xdiag) W.xdiag.ensure((size_t)PMAX_LAUNCH * 256 * 4);
   c->dec_nlaunch = 0;
   c->dec_presplit = persist_presplit(a);
   for (int mt = W.MT; mt >= 1; --mt) {
     const int li = W.MT - mt;  // launch index: its barrier block (armed in taco_infer's state fill)
+    const bool traced = trace_p && li == trace_li;  // one launch is traced
     a.bar = reinterpret_cast<unsigned*>(W.pbar.p) + BAR_WORDS * W.pslot[li];
     a.base_out = W.stat.i() + TS_END + li;
     a.D = make_dev(c, std::min(W.B, 16 * mt));
-    a.trace = li == trace_li ? trace_p : nullptr;
-    a.atrace = li == trace_li ? atrace_p : nullptr;
-    a.diag = xdiag ? static_cast<unsigned*>(xdiag_buf.p) + 256 * li : nullptr;
+    a.trace = traced ? trace_p : nullptr;
+    a.atrace = traced ? trace_p + (size_t)8 * 16 * 256 : nullptr;
+    a.diag = xdiag ? static_cast<unsigned*>(W.xdiag.p) + 256 * li : nullptr;
     // launch timing from the dispatches themselves: ev_dec[0] at the first launch's start, ev_dec[i + 1]
     // at launch i's end (event-record packets between the launches cost ~5 us of idle each)
     launch_persist_decoder(a, mt, s, false, li == 0 ? c->ev_dec[0] : nullptr, c->ev_dec[li + 1]);
-    if (tr && li == trace_li) {  // one launch is traced
-      HIP_OK(hipStreamSynchronize(s));
-      std::vector<unsigned long long> h((size_t)8 * 24 * 256);
-      HIP_OK(hipMemcpy(h.data(), trace_buf.p, h.size() * 8, hipMemcpyDeviceToHost));
-      if (FILE* fp = std::fopen(tr, "wb")) {
-        std::fwrite(h.data(), 8, h.size(), fp);
-        std::fclose(fp);
-      }
-      a.trace = nullptr;
-      a.atrace = nullptr;
-      tr = nullptr;
-    }
+    if (traced) dump_ptrace(tr, W.trace, s);
     c->dec_nlaunch++;
   }
-  a.diag = nullptr;
-  if (xdiag) {  // TTS_DIAG_XCC: print each launch's workgroup -> XCD map and the hand-off addresses
-    HIP_OK(hipStreamSynchronize(s));
-    std::vector<unsigned> h((size_t)PMAX_LAUNCH * 256);
-    HIP_OK(hipMemcpy(h.data(), xdiag_buf.p, h.size() * 4, hipMemcpyDeviceToHost));
-    for (int li = 0; li < c->dec_nlaunch; ++li) {
-      std::fprintf(stderr, "TTS_DIAG_XCC launch %d: wg0 xcc %u, wg0..15:", li, h[li * 256]);
-      for (int k = 0; k < 16; ++k) std::fprintf(stderr, " %u", h[li * 256 + k]);
-      std::fprintf(stderr, "\n");
-    }
-    std::fprintf(stderr, "TTS_DIAG_XCC addresses: bar %p pq %p hatt %p ctx %p hdec0 %p pb %p\n", (void*)W.pbar.p,
-                 (void*)a.pq, (void*)a.hatt, (void*)a.ctx, (void*)a.hdec0, (void*)a.pb);
-  }
+  if (xdiag) print_xdiag(c, a, s);
 }
 
-}  // namespace
+// the whole decode on the persistent kernel (decoder_persist.hip)
+void run_persistent(tts_ctx* c, int r, float thr, hipStream_t s) {
+  build_pj(c, r);
+  grow<float>(c->tws.spkb, (size_t)64 * (8320 + 112 * 16), c->tws.gen);
+  const PArgs a = persist_args(c, r, thr);
+  stage_row_biases(c, a, s);
+  reset_variant_state(c, s);
+  launch_cascade(c, a, s);
+}
 
-void ttsh::taco_infer(tts_ctx* c, const int64_t* ids, const int32_t* h_lens, int B, int T_max, int r,
-                const int32_t* h_max_steps, int S_cap, float thr, float* d_dec, float* d_post, float* d_align,
-                float* d_stop, int32_t* h_steps, int32_t* h_status, void* stream,
-                const int64_t* d_spk_ids, const float* d_spk_emb, const FusedVoc* fv) {
-  auto& M = c->taco;
+// ---- the steps of taco_infer, in call order ----
+
+// returns the largest max_decoder_steps of the batch
+int check_infer_args(const TacoModel& M, const int32_t* h_lens, int B, int T_max, int r, const int32_t* h_max_steps,
+                     int S_cap) {
   TTS_CHECK(M.ready, "tacotron2 weights not finalized");
   TTS_CHECK(B >= 1 && B <= BMAX, "B must be in [1, 64]");
   TTS_CHECK(T_max >= 1 && T_max <= 4096, "T_max must be in [1, 4096]");
@@ -654,102 +681,99 @@ void ttsh::taco_infer(tts_ctx* c, const int64_t* ids, const int32_t* h_lens, int
     max_ms = std::max(max_ms, (int)h_max_steps[b]);
   }
   TTS_CHECK(S_cap >= max_ms, "S_cap < max(max_steps)");
-  taco_workspace(c, B, T_max, S_cap, r);
+  return max_ms;
+}
+
+// Decode order: longest expected first (max_decoder_steps, then text length), so the rows still
+// decoding at the end sit in the first batch tiles and the step can shrink to fewer tiles.
+// Every row is independent, so the order changes nothing but speed; outputs are scattered back.
+// Returns the order (decode row i = caller row perm[i]) and launches TacoSetup.
+std::vector<int> stage_decode_order(tts_ctx* c, const int32_t* h_lens, const int32_t* h_max_steps, int B,
+                                    unsigned* zero_flag, hipStream_t s) {
   auto& W = c->tws;
-  hipStream_t s = c->s;
-  enter(c, stream);
-  // Decode order: longest expected first (max_decoder_steps, then text length), so the rows still
-  // decoding at the end sit in the first batch tiles and the step can shrink to fewer tiles.
-  // Every row is independent, so the order changes nothing but speed; outputs are scattered back.
-  std::vector<int> perm(B), inv(B);
+  std::vector<int> perm(B);
   for (int b = 0; b < B; ++b) perm[b] = b;
   std::stable_sort(perm.begin(), perm.end(), [&](int x, int y) {
     if (h_max_steps[x] != h_max_steps[y]) return h_max_steps[x] > h_max_steps[y];
     return h_lens[x] > h_lens[y];
   });
-  for (int i = 0; i < B; ++i) inv[perm[i]] = i;
-  // decode order, its inverse, lengths and the control block (base = 0, all_done = 0,
-  // active_tiles = MT, done/steps/status = 0, max_steps) in one launch, as kernel arguments
-  {
-    TacoSetup ta{};
-    ta.B = B;
-    ta.MT = W.MT;
-    for (int i = 0; i < B; ++i) {
-      ta.perm[i] = perm[i];
-      ta.inv[i] = inv[i];
-      ta.lens[i] = h_lens[perm[i]];
-      ta.max_steps[i] = h_max_steps[perm[i]];
-    }
-    taco_setup_kernel<<<1, 256, 0, s>>>(ta, W.map.i(), W.lens.i(), W.ctl.i(), fv ? x3_flag(c) : nullptr);
-    HIP_OK(hipGetLastError());
+  // decode order, its inverse, lengths and the control block in one launch, as kernel arguments
+  TacoSetup ta{};
+  ta.B = B;
+  ta.MT = W.MT;
+  for (int i = 0; i < B; ++i) {
+    ta.perm[i] = perm[i];
+    ta.inv[perm[i]] = i;
+    ta.lens[i] = h_lens[perm[i]];
+    ta.max_steps[i] = h_max_steps[perm[i]];
   }
-  int* d_map = W.map.i();
-  W.thr = thr;
-  // speaker vectors in decode order: external embeddings, or rows of the learned table
-  TTS_CHECK(!M.variant() || use_persistent(c), "BN prenet / attention windowing / forward / Graves attention run on "
-                                               "the persistent decoder only (<= 64 utterances per call on a 256-CU "
-                                               "device)");
-  if (M.spk_dim) {
-    TTS_CHECK(d_spk_ids || d_spk_emb, "multi-speaker model: speaker ids or speaker embeddings are required");
-    TTS_CHECK(use_persistent(c), "multi-speaker decoding runs on the persistent decoder only (<= 64 utterances "
-                                 "per call on a 256-CU device)");
-    if (d_spk_emb) {
-      gather_rows<float>(d_spk_emb, W.spk.f(), d_map, M.spk_dim, B, s);
-    } else {
-      TTS_CHECK(M.num_spk > 0, "model has no speaker_embedding table: pass speaker embeddings");
-      gather_rows<int64_t>(d_spk_ids, reinterpret_cast<int64_t*>(W.spkid.p), d_map, 1, B, s);
-      launch_embed_gather(reinterpret_cast<const int64_t*>(W.spkid.p), 1, M.spk_table.f(), M.num_spk, M.spk_dim,
-                          W.lens.i(), B, W.spk.f(), s);
-    }
+  taco_setup_kernel<<<1, 256, 0, s>>>(ta, W.map.i(), W.lens.i(), ctl_block(W), zero_flag);
+  HIP_OK(hipGetLastError());
+  return perm;
+}
+
+// speaker vectors in decode order: external embeddings, or rows of the learned table
+void stage_speakers(tts_ctx* c, const int64_t* d_spk_ids, const float* d_spk_emb, int B, hipStream_t s) {
+  auto& M = c->taco;
+  auto& W = c->tws;
+  if (!M.spk_dim) return;
+  TTS_CHECK(d_spk_ids || d_spk_emb, "multi-speaker model: speaker ids or speaker embeddings are required");
+  TTS_CHECK(use_persistent(c), "multi-speaker decoding runs on the persistent decoder only (<= 64 utterances "
+                               "per call on a 256-CU device)");
+  if (d_spk_emb) {
+    gather_rows<float>(d_spk_emb, W.spk.f(), W.map.i(), M.spk_dim, B, s);
+  } else {
+    TTS_CHECK(M.num_spk > 0, "model has no speaker_embedding table: pass speaker embeddings");
+    gather_rows<int64_t>(d_spk_ids, reinterpret_cast<int64_t*>(W.spkid.p), W.map.i(), 1, B, s);
+    launch_embed_gather(reinterpret_cast<const int64_t*>(W.spkid.p), 1, M.spk_table.f(), M.num_spk, M.spk_dim,
+                        W.lens.i(), B, W.spk.f(), s);
   }
-  // encoder + processed inputs
-  run_encoder(c, ids, B, T_max, W.enc.f(), s, d_map);
-  {
-    ConvCall cc;
-    cc.lens = W.lens.i();
-    cc.B = B;
-    cc.oflow = x3_flag(c);
-    cc.max_q = T_max;
-    cc.s[0] = src_of(W.enc.f(), (long)T_max * 512, 1, 512, 512, 0);
-    cc.out = W.penc.f();
-    cc.ob = (long)T_max * 128;
-    cc.oc = 1;
-    cc.ot = 128;
-    run_conv(M.penc, cc, s);
-  }
-  // decoder state
+}
+
+// encoder (rows in decode order) + processed inputs
+void run_encoder_penc(tts_ctx* c, const int64_t* ids, int B, int T_max, hipStream_t s) {
+  auto& W = c->tws;
+  run_encoder(c, ids, B, T_max, W.enc.f(), s, W.map.i());
+  ConvCall cc;
+  cc.lens = W.lens.i();
+  cc.B = B;
+  cc.oflow = x3_flag(c);
+  cc.max_q = T_max;
+  cc.s[0] = src_of(W.enc.f(), (long)T_max * 512, 1, 512, 512, 0);
+  cc.out = W.penc.f();
+  cc.ob = (long)T_max * 128;
+  cc.oc = 1;
+  cc.ot = 128;
+  run_conv(c->taco.penc, cc, s);
+}
+
+// decoder state and outputs zeroed in one launch (the postnet output too, and the persistent
+// launches' barrier blocks), attention_rnn gate biases broadcast
+void fill_decoder_state(tts_ctx* c, int B, int T_max, int S_cap, int r, bool persist, hipStream_t s) {
+  auto& M = c->taco;
+  auto& W = c->tws;
   const int Bp = W.MT * 16;
-  const bool persist = use_persistent(c);
-  if (persist && !W.pslot_cal) {  // ordered after the caller's work (enter above) and this call's encoder
-    pick_barrier_blocks(reinterpret_cast<unsigned*>(W.pbar.p), PBAR_CAND, PMAX_LAUNCH, W.pslot, s);
-    W.pslot_cal = true;
-  }
-  {
-    FillList f;  // decoder state and outputs zeroed in one launch (the postnet output too)
-    f.add(W.catt.p, (size_t)Bp * 1024 * 4);
-    f.add(W.hatt.p, (size_t)Bp * 1024 * 4);
-    f.add(W.hdec0.p, (size_t)Bp * 1024 * 4);
-    f.add(W.hdec1.p, (size_t)Bp * 1024 * 4);
-    f.add(W.cdec.p, (size_t)Bp * 1024 * 4);
-    f.add(W.ctx.p, (size_t)Bp * 512 * 4);
-    f.add(W.y.p, (size_t)Bp * 80 * M.r_init * 4);
-    f.add(W.alpha.p, (size_t)B * T_max * 4);
-    f.add(W.acum.p, (size_t)B * T_max * 4);
-    f.add(W.dec.p, (size_t)B * S_cap * r * 80 * 4);
-    f.add(W.align.p, (size_t)B * S_cap * T_max * 4);
-    f.add(W.stop.p, (size_t)B * S_cap * 4);
-    f.add(W.acnt.p, BMAX * sizeof(unsigned));
-    f.add(W.post.p, (size_t)B * S_cap * r * 80 * 4);
-    if (persist)
-      for (int li = 0; li < W.MT; ++li) add_barrier_fills(f, reinterpret_cast<unsigned*>(W.pbar.p) + BAR_WORDS * W.pslot[li], 1);
-    launch_fills(f, s);
-  }
+  FillList f;
+  for (const DevBuf* b : {&W.catt, &W.hatt, &W.hdec0, &W.hdec1, &W.cdec}) f.add(b->p, (size_t)Bp * 1024 * 4);
+  f.add(W.ctx.p, (size_t)Bp * 512 * 4);
+  f.add(W.y.p, (size_t)Bp * 80 * M.r_init * 4);
+  f.add(W.alpha.p, (size_t)B * T_max * 4);
+  f.add(W.acum.p, (size_t)B * T_max * 4);
+  f.add(W.dec.p, (size_t)B * S_cap * r * 80 * 4);
+  f.add(W.align.p, (size_t)B * S_cap * T_max * 4);
+  f.add(W.stop.p, (size_t)B * S_cap * 4);
+  f.add(W.acnt.p, BMAX * sizeof(unsigned));
+  f.add(W.post.p, (size_t)B * S_cap * r * 80 * 4);
+  if (persist)
+    for (int li = 0; li < W.MT; ++li) add_barrier_fills(f, reinterpret_cast<unsigned*>(W.pbar.p) + BAR_WORDS * W.pslot[li], 1);
+  launch_fills(f, s);
   bcast_rows_kernel<<<256, 256, 0, s>>>(M.att_bias.f(), 4096, W.gatt.f(), Bp);
   HIP_OK(hipGetLastError());
-  c->dec_path = persist ? 1 : 0;
-  if (persist) {
-    run_persistent(c, r, thr, s);
-  } else {
+}
+
+// the decode as captured CHUNK-step graphs (decoder.hip's per-step kernels), polled by the host
+void run_graph_decoder(tts_ctx* c, int B, int T_max, int S_cap, int r, float thr, int max_ms, hipStream_t s) {
+  auto& W = c->tws;
   // step graphs, cached per configuration / buffer generation
   if (W.graph_gen != W.gen || W.gB != B || W.gT != T_max || W.gS != S_cap || W.gr != r || W.gthr != thr) {
     for (auto& ge : W.graphs)
@@ -772,64 +796,109 @@ void ttsh::taco_infer(tts_ctx* c, const int64_t* ids, const int32_t* h_lens, int
   int mt = W.MT;
   for (int ch = 0; ch < chunks_max && !done; ++ch) {
     HIP_OK(hipGraphLaunch(W.graphs[mt], s));
-    HIP_OK(hipMemcpyAsync(&c->pinned[2 * (ch & 1)], &reinterpret_cast<DecCtl*>(W.ctl.p)->all_done, 8,
-                          hipMemcpyDeviceToHost, s));
+    // {all_done, active_tiles} into the polling pair of this chunk's parity
+    HIP_OK(hipMemcpyAsync(&c->pinned[PIN_CHUNK + 2 * (ch & 1)], &ctl_block(W)->ctl.all_done, 8, hipMemcpyDeviceToHost, s));
     HIP_OK(hipEventRecord(c->ev_chunk[ch & 1], s));
     if (ch >= 1) {
       HIP_OK(hipEventSynchronize(c->ev_chunk[(ch - 1) & 1]));
-      const int* pv = &c->pinned[2 * ((ch - 1) & 1)];
+      const int* pv = &c->pinned[PIN_CHUNK + 2 * ((ch - 1) & 1)];
       if (pv[0]) done = true;
       else if (pv[1] >= 1 && pv[1] < mt) mt = pv[1];
     }
   }
-  }
-  // postnet over each row's own frames: lengths from the decoder results on the device, grid sized
-  // by S_cap (tiles past a row's length exit at entry), so the decode needs no host round trip
-  taco_mlens_kernel<<<1, 64, 0, s>>>(W.ctl.i(), B, r, W.mlens.i());
+}
+
+// postnet over each row's own frames: lengths from the decoder results on the device, grid sized
+// by S_cap (tiles past a row's length exit at entry), so the decode needs no host round trip; then
+// the scatter back to the caller's row order: output row b <- decode row inv[b]
+void run_postnet_scatter(tts_ctx* c, int B, int T_max, int S_cap, int r, float* d_dec, float* d_post, float* d_align,
+                         float* d_stop, hipStream_t s) {
+  auto& W = c->tws;
+  taco_mlens_kernel<<<1, 64, 0, s>>>(ctl_block(W), B, r, W.mlens.i());
   HIP_OK(hipGetLastError());
   const long fb = (long)S_cap * r * 80;  // W.post was zeroed with the decoder state
   run_postnet(c, W.dec.f(), fb, W.mlens.i(), B, S_cap * r, S_cap * r, W.post.f(), fb, s);
-  // scatter back to the caller's row order: output row b <- decode row inv[b]
   gather4_rows(Gather4{{W.post.f(), W.dec.f(), W.align.f(), W.stop.f()}, {d_post, d_dec, d_align, d_stop},
                        {fb, fb, (long)S_cap * T_max, (long)S_cap}},
-               d_map + BMAX, B, s);
-  // one host round trip per call: barrier error words, per-row results, range flag, launch steps
-  {
-    const unsigned* lc = reinterpret_cast<const unsigned*>(W.lc.p);
-    taco_status_kernel<<<1, 256, 0, s>>>(W.enc_persist ? lc : nullptr, W.enc_ndom,
-                                         persist ? reinterpret_cast<const unsigned*>(W.pbar.p) : nullptr,
-                                         DecSlots{{W.pslot[0], W.pslot[1], W.pslot[2], W.pslot[3]}}, c->dec_nlaunch, W.ctl.i(), c->gemm_x3 ? x3_flag(c) : nullptr, W.stat.i(),
-                                         B, d_map + BMAX, r, fv ? fv->Lmin : 0, fv ? fv->vlens : nullptr);
-    HIP_OK(hipGetLastError());
-    int* pin = c->pinned;
-    HIP_OK(hipMemcpyAsync(pin + TS_ENC, W.stat.i() + TS_ENC, (TS_N - TS_ENC) * 4, hipMemcpyDeviceToHost, s));
-    if (fv) {  // the vocoder goes in behind the status words; the host waits for the words only
-      HIP_OK(hipEventRecord(c->ev_status, s));
-      fv->enqueue();
-      HIP_OK(hipEventSynchronize(c->ev_status));
-    } else {
-      HIP_OK(hipStreamSynchronize(s));
-    }
-    TTS_CHECK(!W.enc_persist || (pin[TS_ENC] == 0 && pin[TS_ENC + 1] == 0 && pin[TS_ENC + 2] == 0 && pin[TS_ENC + 3] == 0),
-              "persistent BiLSTM: grid barrier timed out (workgroups not co-resident) or preempted past "
-              "TTS_BARRIER_TIMEOUT_MS; retrying the call is safe)");
-    TTS_CHECK(!persist || (pin[TS_DEC] == 0 && pin[TS_DEC + 1] == 0 && pin[TS_DEC + 2] == 0 && pin[TS_DEC + 3] == 0),
-              "persistent decoder: grid barrier timed out (workgroups not co-resident) or preempted past "
-              "TTS_BARRIER_TIMEOUT_MS; retrying the call is safe)");
-    if (c->gemm_x3) {  // with_x3_fallback reads the flag from here
-      pin[12] = pin[TS_FLAG];
-      c->flag_read = true;
-    }
-    for (int i = 0; i < PMAX_LAUNCH; ++i) c->dec_end[i] = persist && i < c->dec_nlaunch ? pin[TS_END + i] : 0;
-    TTS_CHECK(!fv || pin[TS_VERR] == 0, VOC_SHORT_MSG);
+               W.map.i() + BMAX, B, s);
+}
+
+// one host round trip per call: barrier error words, per-row results, range flag, launch steps
+// gathered by one kernel and copied to the pinned page; a fused call's vocoder goes in behind the
+// copy, and the host waits for the words only
+void read_status(tts_ctx* c, int B, int r, bool persist, const FusedVoc* fv, hipStream_t s) {
+  auto& W = c->tws;
+  const unsigned* lc = reinterpret_cast<const unsigned*>(W.lc.p);
+  DecSlots ds;
+  std::copy(W.pslot, W.pslot + PMAX_LAUNCH, ds.v);
+  taco_status_kernel<<<1, 256, 0, s>>>(W.enc_persist ? lc : nullptr, W.enc_ndom,
+                                       persist ? reinterpret_cast<const unsigned*>(W.pbar.p) : nullptr, ds,
+                                       c->dec_nlaunch, ctl_block(W), c->gemm_x3 ? x3_flag(c) : nullptr, W.stat.i(), B,
+                                       W.map.i() + BMAX, r, fv ? fv->Lmin : 0, fv ? fv->vlens : nullptr);
+  HIP_OK(hipGetLastError());
+  int* pin = c->pinned;
+  HIP_OK(hipMemcpyAsync(pin + TS_ENC, W.stat.i() + TS_ENC, (TS_N - TS_ENC) * 4, hipMemcpyDeviceToHost, s));
+  if (fv) {
+    HIP_OK(hipEventRecord(c->ev_status, s));
+    fv->enqueue();
+    HIP_OK(hipEventSynchronize(c->ev_status));
+  } else {
+    HIP_OK(hipStreamSynchronize(s));
   }
+  TTS_CHECK(!W.enc_persist || all_zero(pin + TS_ENC, ENC_NDOM_MAX), ENC_BAR_MSG);
+  TTS_CHECK(!persist || all_zero(pin + TS_DEC, PMAX_LAUNCH),
+            "persistent decoder: grid barrier timed out (workgroups not co-resident) or preempted past "
+            "TTS_BARRIER_TIMEOUT_MS; retrying the call is safe)");
+  if (c->gemm_x3) {  // with_x3_fallback reads the flag from here
+    pin[PIN_FLAG] = pin[TS_FLAG];
+    c->flag_read = true;
+  }
+  for (int i = 0; i < PMAX_LAUNCH; ++i) c->dec_end[i] = persist && i < c->dec_nlaunch ? pin[TS_END + i] : 0;
+  TTS_CHECK(!fv || pin[TS_VERR] == 0, VOC_SHORT_MSG);
+}
+
+// the rows' steps and status from the status words (decode order) to the caller's order
+void report_rows(tts_ctx* c, const std::vector<int>& perm, int32_t* h_steps, int32_t* h_status) {
   const int* res = c->pinned + TS_RES;
-  for (int i = 0; i < B; ++i) {
+  for (size_t i = 0; i < perm.size(); ++i) {
     TTS_CHECK(res[i] == 1, "decoder did not finish an utterance (internal error)");
     const int b = perm[i];
     h_steps[b] = res[BMAX + i];
     h_status[b] = res[2 * BMAX + i];
   }
+}
+
+}  // namespace
+
+void ttsh::taco_infer(tts_ctx* c, const int64_t* ids, const int32_t* h_lens, int B, int T_max, int r,
+                const int32_t* h_max_steps, int S_cap, float thr, float* d_dec, float* d_post, float* d_align,
+                float* d_stop, int32_t* h_steps, int32_t* h_status, void* stream,
+                const int64_t* d_spk_ids, const float* d_spk_emb, const FusedVoc* fv) {
+  const int max_ms = check_infer_args(c->taco, h_lens, B, T_max, r, h_max_steps, S_cap);
+  taco_workspace(c, B, T_max, S_cap, r);
+  auto& W = c->tws;
+  hipStream_t s = c->s;
+  enter(c, stream);
+  // a fused call's range flag is zeroed by the setup launch (no separate fill)
+  const std::vector<int> perm = stage_decode_order(c, h_lens, h_max_steps, B, fv ? x3_flag(c) : nullptr, s);
+  W.thr = thr;
+  const bool persist = use_persistent(c);
+  TTS_CHECK(!c->taco.variant() || persist, "BN prenet / attention windowing / forward / Graves attention run on "
+                                           "the persistent decoder only (<= 64 utterances per call on a 256-CU "
+                                           "device)");
+  stage_speakers(c, d_spk_ids, d_spk_emb, B, s);
+  run_encoder_penc(c, ids, B, T_max, s);
+  if (persist && !W.pslot_cal) {  // ordered after the caller's work (enter above) and this call's encoder
+    pick_barrier_blocks(reinterpret_cast<unsigned*>(W.pbar.p), PBAR_CAND, PMAX_LAUNCH, W.pslot, s);
+    W.pslot_cal = true;
+  }
+  fill_decoder_state(c, B, T_max, S_cap, r, persist, s);
+  c->dec_path = persist ? 1 : 0;
+  if (persist) run_persistent(c, r, thr, s);
+  else run_graph_decoder(c, B, T_max, S_cap, r, thr, max_ms, s);
+  run_postnet_scatter(c, B, T_max, S_cap, r, d_dec, d_post, d_align, d_stop, s);
+  read_status(c, B, r, persist, fv, s);
+  report_rows(c, perm, h_steps, h_status);
   if (fv)  // the caller's stream waits for the decode's outputs here, for the vocoder at finish
     HIP_OK(hipStreamWaitEvent((hipStream_t)stream, c->ev_status, 0));
   else
@@ -961,16 +1030,16 @@ int tts_time_decoder_kernel(tts_ctx* c, int which, int iters, float* ms_out) {
     auto& W = c->tws;
     hipStream_t s = c->s;
     // live state of the last decode, re-armed: base = 1, nothing done, unbounded max steps
-    std::vector<int> ctl(4 + 4 * BMAX, 0);
-    ctl[0] = 1;
-    for (int b = 0; b < BMAX; ++b) ctl[4 + 3 * BMAX + b] = 1 << 30;
+    DecCtlBlock ctl{};
+    ctl.ctl.base = 1;
+    std::fill(ctl.max_steps, ctl.max_steps + BMAX, 1 << 30);
     hipEvent_t e0, e1;
     HIP_OK(hipEventCreate(&e0));
     HIP_OK(hipEventCreate(&e1));
-    HIP_OK(hipMemcpyAsync(W.ctl.p, ctl.data(), ctl.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(W.ctl.p, &ctl, sizeof(ctl), hipMemcpyHostToDevice, s));
     if (which == 0) enqueue_step(c, 0, 0, s, W.MT);  // warm-up
     else HIP_OK(hipGraphLaunch(W.graphs[W.MT], s));
-    HIP_OK(hipMemcpyAsync(W.ctl.p, ctl.data(), ctl.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(W.ctl.p, &ctl, sizeof(ctl), hipMemcpyHostToDevice, s));
     HIP_OK(hipEventRecord(e0, s));
     for (int i = 0; i < iters; ++i) {
       if (which == 0) enqueue_step(c, 0, 0, s, W.MT);
@@ -984,8 +1053,8 @@ int tts_time_decoder_kernel(tts_ctx* c, int which, int iters, float* ms_out) {
     HIP_OK(hipEventElapsedTime(&ms, e0, e1));
     *ms_out = which == 0 ? ms / iters : ms / (iters * CHUNK);
     // leave the control block in a finished state
-    ctl[1] = 1;
-    HIP_OK(hipMemcpy(W.ctl.p, ctl.data(), ctl.size() * 4, hipMemcpyHostToDevice));
+    ctl.ctl.all_done = 1;
+    HIP_OK(hipMemcpy(W.ctl.p, &ctl, sizeof(ctl), hipMemcpyHostToDevice));
     HIP_OK(hipEventDestroy(e0));
     HIP_OK(hipEventDestroy(e1));
   });

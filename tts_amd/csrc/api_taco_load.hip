@@ -291,7 +291,7 @@ void ttsh::taco_workspace(tts_ctx* c, int B, int T_max, int S_cap, int r) {
   grow<float>(W.apm, (size_t)B * nch, g);
   grow<float>(W.apu, (size_t)B * nch * 512, g);
   grow<unsigned>(W.acnt, BMAX, g);
-  grow<int>(W.ctl, 4 + 4 * BMAX, g);
+  grow<DecCtlBlock>(W.ctl, 1, g);
   grow<float>(W.dec, (size_t)B * S_cap * r * 80, g);
   grow<float>(W.align, (size_t)B * S_cap * T_max, g);
   grow<float>(W.stop, (size_t)B * S_cap, g);

@@ -2,6 +2,8 @@
 #pragma once
 #include "common.h"
 
+#include <cstddef>
+
 enum { EPI_STORE = 0, EPI_LSTM = 1 };
 
 // GEMM activations live in HBM in MFMA fragment order so that one wave's A-operand load of a
@@ -59,6 +61,18 @@ struct DecCtl {
   int active_tiles;  // 1 + (largest unfinished row) / 16: the host drops to a smaller batch tile
   int pad1;
 };
+
+// The decoder control block on the device (TacoWS::ctl): what DecDev's ctl / done / steps / status /
+// max_steps point into. done | steps | status are read back as one run of 3 * BMAX ints (TS_RES).
+struct DecCtlBlock {
+  DecCtl ctl;
+  int done[BMAX], steps[BMAX], status[BMAX];  // status: 1 = stopnet, 2 = max_decoder_steps
+  int max_steps[BMAX];
+};
+static_assert(sizeof(DecCtlBlock) == (4 + 4 * BMAX) * 4 && offsetof(DecCtlBlock, done) == 4 * 4 &&
+                  offsetof(DecCtlBlock, steps) == (4 + BMAX) * 4 && offsetof(DecCtlBlock, status) == (4 + 2 * BMAX) * 4 &&
+                  offsetof(DecCtlBlock, max_steps) == (4 + 3 * BMAX) * 4,
+              "control block layout: [DecCtl | done | steps | status | max_steps]");
 
 struct DecDev {
   DecCtl* ctl;

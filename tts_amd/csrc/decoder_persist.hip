@@ -35,8 +35,10 @@
 #include "split16.h"
 
 #include <algorithm>
+#include <array>
 #include <cstdio>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 namespace {
@@ -53,18 +55,23 @@ constexpr int PTC = 32;      // attention positions per work item
 constexpr int IW0 = NATT;    // attention items live on workgroups IW0 .. PW-1 (round-robin)
 constexpr int YROWS = 64;    // rows per projection half (independent of the batch tile: the MT = 1
                              // launch reads what the MT = 2 launch left)
+// the decoder variants compiled into persist_decoder_kernel<MT, VAR>, as bits of VAR: attention
+// windowing, forward attention, Graves attention (which replaces the location-sensitive attention,
+// so it excludes the other two), P3's attention_rnn prenet part on the split-f16 MFMA (attp_x3 given)
+constexpr int V_WIN = 1, V_FWD = 2, V_GRAVES = 4, V_X3 = 8, V_N = 16;
+constexpr bool var_valid(int VAR) { return !(VAR & V_GRAVES) || !(VAR & (V_WIN | V_FWD)); }
 // encoder rows (of 8 per thread) an attention item keeps in registers across steps: 4 where the
 // kernel stays within 256 VGPRs without spills (split-f16 variants without forward attention), 0
 // elsewhere (and for 48 / 64-row batch tiles, whose accumulators need the registers); pec_arr
 // sizes the (unused) array of the latter
-constexpr int pec_of(int VAR, int MT) { return ((VAR & 8) && !(VAR & 2) && MT <= 2) ? 4 : 0; }
+constexpr int pec_of(int VAR, int MT) { return ((VAR & V_X3) && !(VAR & V_FWD) && MT <= 2) ? 4 : 0; }
 constexpr int pec_arr(int VAR, int MT) { return pec_of(VAR, MT) > 0 ? pec_of(VAR, MT) : 1; }
-// pre-split hand-offs (VAR 8: location attention, every decoder GEMM on the split-f16 MFMA): h_att,
+// pre-split hand-offs (VAR = V_X3 alone: location attention, every decoder GEMM on the split-f16 MFMA): h_att,
 // ctx and h_dec are published as their f16 hi / lo halves, [hi 0..3 | lo 0..3] in the 16 bytes a
 // fragment quad takes in fp32, so the streaming consumers feed the loads to the MFMA without
 // splitting (the split is done once, by the producer; tools/payload_bench.hip mode 3: 0.42 us less
 // per streamed 192 KB block). The variants with fp32 readers of these buffers keep fp32.
-constexpr bool presplit_of(int VAR) { return VAR == 8; }
+constexpr bool presplit_of(int VAR) { return VAR == V_X3; }
 template <bool PS>
 __device__ __forceinline__ void stc_quad_h(float* base, int e, float v) {
   if constexpr (PS) stc_quad_x3(base, e, v);
@@ -244,7 +251,7 @@ __device__ __forceinline__ void pattn_item(const PArgs& P, int t, int b, int ch,
                                            int* is_last, float (&L)[8], bool haveL,
                                            f32x4 (&evc)[pec_arr(VAR, MT)], bool load_ev, float* ekeep) {
   constexpr int PEC = pec_of(VAR, MT);
-  constexpr bool WIN = VAR & 1, FWD = (VAR & 2) != 0;  // compiled-in decoder variants
+  constexpr bool WIN = VAR & V_WIN, FWD = (VAR & V_FWD) != 0;  // compiled-in decoder variants
   constexpr int NT = PT, TC = PTC;
   constexpr int NPT = NPQ_ / 16;  // query partials per thread (16 groups)
   constexpr int Bp = MT * 16;
@@ -958,9 +965,9 @@ constexpr size_t P_LDS = P_LDS_APRE + P_LDS_WC + P_LDS_SCRATCH + P_LDS_EKEEP;
 
 template <int MT, int VAR>
 __global__ __launch_bounds__(PT) void persist_decoder_kernel(PArgs P) {
-  constexpr bool GRAVES = (VAR & 4) != 0;  // Graves attention replaces the location-sensitive one
-  constexpr bool X3P = (VAR & 8) != 0;     // P3's attention_rnn prenet part on the split-f16 MFMA
-  constexpr bool DEFER = (VAR & 7) == 0;   // plain location attention: alignment pass deferred to P6
+  constexpr bool GRAVES = (VAR & V_GRAVES) != 0;  // Graves attention replaces the location-sensitive one
+  constexpr bool X3P = (VAR & V_X3) != 0;     // P3's attention_rnn prenet part on the split-f16 MFMA
+  constexpr bool DEFER = (VAR & (V_WIN | V_FWD | V_GRAVES)) == 0;  // plain location attention: alignment pass deferred to P6
   constexpr bool PS = presplit_of(VAR);    // h_att, ctx, h_dec published pre-split
   extern __shared__ __attribute__((aligned(16))) f32x4 smem4[];
   __shared__ int sflag, is_last;
@@ -1745,8 +1752,18 @@ bool persist_trace_built() { return false; }
 #endif
 bool persist_defer_ok(int nitems) { return nitems <= (PW - IW0) * PDEF_MAXIT; }
 
+template <int MT, int VAR>
+const void* pdk() {
+  if constexpr (var_valid(VAR)) return (const void*)persist_decoder_kernel<MT, VAR>;
+  else return nullptr;
+}
+template <int MT, int... V>
+std::array<const void*, V_N> pdk_row(std::integer_sequence<int, V...>) {
+  return {pdk<MT, V>()...};
+}
+
 static int persist_var(const PArgs& a) {
-  return (a.gK > 0 ? 4 : (a.win ? 1 : 0) | (a.fwd ? 2 : 0)) | (a.attp_x3 ? 8 : 0);
+  return (a.gK > 0 ? V_GRAVES : (a.win ? V_WIN : 0) | (a.fwd ? V_FWD : 0)) | (a.attp_x3 ? V_X3 : 0);
 }
 bool persist_presplit(const PArgs& a) { return presplit_of(persist_var(a)); }
 
@@ -1756,18 +1773,12 @@ void launch_persist_decoder(const PArgs& a, int MT, hipStream_t s, bool arm, hip
   TTS_CHECK(a.D.B <= 64 && NATT * 4 * 4 == 1024, "persistent decoder: attention_rnn layout");
   TTS_CHECK(a.nchmax * PTC >= a.D.T_max, "persistent decoder: attention partial buffers too small");
   TTS_CHECK(a.D.B <= 16 * MT, "persistent decoder: rows beyond the batch tile");
-  // decoder variants are compiled in only where used: VAR bit 0 windowing, bit 1 forward attention
-  // (bit 2: Graves attention, exclusive of the others); bit 3: split-f16 P3 (attp_x3 given)
   TTS_CHECK(!a.attp_x3 || (a.x3flag && a.dec_x3 && a.apre_x3 && a.pj_x3),
             "persistent decoder: split-f16 weights incomplete or without a range flag");
   const int var = persist_var(a);
-#define PDK(mt, v) (const void*)persist_decoder_kernel<mt, v>
-#define PDK_ROW(mt) \
-  {PDK(mt, 0), PDK(mt, 1), PDK(mt, 2), PDK(mt, 3), PDK(mt, 4), nullptr, nullptr, nullptr, PDK(mt, 8), PDK(mt, 9), \
-   PDK(mt, 10), PDK(mt, 11), PDK(mt, 12)}
-  static const void* const fns[4][13] = {PDK_ROW(1), PDK_ROW(2), PDK_ROW(3), PDK_ROW(4)};
-#undef PDK_ROW
-#undef PDK
+  // the variants are compiled in only where valid (var_valid); the other entries stay null
+  constexpr std::make_integer_sequence<int, V_N> vs{};
+  static const std::array<const void*, V_N> fns[4] = {pdk_row<1>(vs), pdk_row<2>(vs), pdk_row<3>(vs), pdk_row<4>(vs)};
   const void* f = fns[MT - 1][var];
   TTS_CHECK(f != nullptr, "persistent decoder: variant");
   ensure_dyn_lds(f, (int)P_LDS);

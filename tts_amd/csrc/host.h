@@ -17,7 +17,6 @@
 namespace ttsh {
 
 constexpr int CHUNK = 8;  // decoder steps per captured graph (even: parity of t == parity of j)
-constexpr int BMAX = 64;  // utterances per call (Bp <= 64)
 
 struct DevBuf {
   void* p = nullptr;
@@ -169,13 +168,23 @@ struct TacoModel {
 // Tacotron2 status words (TacoWS::stat on the device, tts_ctx::pinned on the host; one copy after
 // the call): BiLSTM barrier errors (one per recurrence: 2 directions x up to 2 row groups),
 // persistent-decoder barrier errors (one per launch), the decoder results (done, steps, status per
-// decode row), the range flag, the launches' end steps
+// decode row: DecCtlBlock's three arrays), the range flag, the launches' end steps
 constexpr int PMAX_LAUNCH = 4;  // persistent decoder launches per decode (MT = 4, 3, 2, 1)
 constexpr int PBAR_CAND = 16;   // candidate barrier blocks timed for them
 constexpr int ENC_NDOM_MAX = 4;  // BiLSTM recurrences (barrier blocks) per launch
 constexpr int TS_ENC = 16, TS_DEC = TS_ENC + ENC_NDOM_MAX, TS_RES = TS_DEC + PMAX_LAUNCH, TS_FLAG = TS_RES + 3 * BMAX,
               TS_END = TS_FLAG + 1, TS_VERR = TS_END + PMAX_LAUNCH, TS_N = TS_VERR + 1;
-static_assert(TS_N <= 240, "status words fit the pinned block below check_encoder_barrier's words");
+// The pinned status page (tts_ctx::pinned, PIN_N ints), by region:
+//   [PIN_CHUNK, + 4)            graph decoder chunk polling: {all_done, active_tiles} of chunk parity 0 / 1
+//   [PIN_FLAG]                  range flag of the call (with_x3_fallback)
+//   [TS_ENC, TS_N)              status words of the last Tacotron2 call (one copy of TacoWS::stat)
+//   [PIN_ENC, + ENC_NDOM_MAX)   BiLSTM barrier error words of tts_taco_encoder
+//   [TK_PIN, + NVT)             range flag of the vocoder of ticket slot k
+constexpr int NVT = 4;  // fused-call ticket slots
+constexpr int PIN_CHUNK = 0, PIN_FLAG = 12, PIN_ENC = 240, TK_PIN = 248, PIN_N = 256;
+static_assert(PIN_CHUNK + 4 <= PIN_FLAG && PIN_FLAG < TS_ENC && TS_N <= PIN_ENC && PIN_ENC + ENC_NDOM_MAX <= TK_PIN &&
+                  TK_PIN + NVT <= PIN_N,
+              "pinned page regions overlap or leave the page");
 
 struct TacoWS {
   int B = 0, T_max = 0, S_cap = 0, r = 0, MT = 0;
@@ -327,7 +336,6 @@ struct AudioWS {
 
 // one submitted fused call: what its fp32 re-run needs if the split-f16 vocoder raised the range
 // flag (the caller keeps d_post and d_wav untouched until the ticket is finished)
-constexpr int NVT = 4, TK_PIN = 248;
 struct VocTicket {
   int64_t id = 0;
   bool pending = false;       // not finished: the caller's stream is not yet ordered after the vocoder
@@ -349,10 +357,8 @@ struct tts_ctx {
   hipEvent_t ev_in = nullptr, ev_out = nullptr, ev_chunk[2] = {nullptr, nullptr};
   hipEvent_t ev_dec[ttsh::PMAX_LAUNCH + 1] = {};  // around the persistent decoder launches
   hipEvent_t ev_status = nullptr;  // a fused call's decode status words are on the host
-  int* pinned = nullptr;  // [256]: [0:4) chunk polling, [12] range flag, [TS_*]: status words of the last
-                          // Tacotron2 call (one copy of TacoWS::stat), [240:244) BiLSTM barrier
-                          // words, [TK_PIN + k]: range flag of the vocoder of ticket slot k
-  bool flag_read = false; // the entry point already fetched the range flag into pinned[12]
+  int* pinned = nullptr;  // [PIN_N] host-pinned status page (regions: PIN_* / TS_* / TK_PIN above)
+  bool flag_read = false; // the entry point already fetched the range flag into pinned[PIN_FLAG]
   int dec_end[ttsh::PMAX_LAUNCH] = {};  // step index after each persistent launch of the last decode
   int dec_path = 0;       // last decode: 0 = step graphs, 1 = persistent kernel
   bool dec_presplit = false;  // last persistent decode published h_att / ctx / h_dec pre-split
@@ -455,11 +461,11 @@ void with_x3_fallback(tts_ctx* c, F&& fn) {
   c->flag_read = false;
   fn();
   if (!c->flag_read) {  // fn may have fetched it with its own status words (taco_infer)
-    HIP_OK(hipMemcpyAsync(&c->pinned[12], flag, 4, hipMemcpyDeviceToHost, c->s));
+    HIP_OK(hipMemcpyAsync(&c->pinned[PIN_FLAG], flag, 4, hipMemcpyDeviceToHost, c->s));
     HIP_OK(hipStreamSynchronize(c->s));
   }
   c->flag_read = false;
-  if (c->pinned[12]) {
+  if (c->pinned[PIN_FLAG]) {
     c->x3_fallbacks++;
     c->gemm_x3 = false;
     try {
