@@ -138,6 +138,35 @@ int tts_taco_postnet(tts_ctx* ctx, const float* d_dec, const int32_t* h_lens, in
 int tts_taco_decoder_state(tts_ctx* ctx, int B, int T_max, float* d_att_h, float* d_att_c, float* d_dec_h,
                            float* d_dec_c, float* d_context, float* d_alpha, float* d_alpha_cum, void* stream);
 
+/* ---- Tacotron (v1): CBHG encoder, GRU decoder, CBHG postnet (TTS/tts/models/tacotron.py) ----
+   Single speaker, no GST, original location-sensitive attention, original prenet.
+   tts_tacotron1_set_tensor/finalize <- Tacotron(...).load_state_dict: tensors by their reference keys
+                       (coarse_decoder.* / decoder_backward.* are not needed); BatchNorm is folded at
+                       finalize. r_init = the constructor's r (proj_to_mel has 80 * r_init rows),
+                       memory_size as given to the constructor (<= 0: the prenet reads the last frame;
+                       at most 32), attn_norm 0 = sigmoid / 1 = softmax, postnet_output_dim = rows of
+                       last_linear.
+   tts_tacotron1_infer <- Tacotron.inference, batched: output i equals the reference B = 1 call on
+                       utterance i. Arguments as tts_taco_infer except: no stop threshold (the
+                       reference's literals: after step t, stop if t > T/4 and (sigmoid(stop) > 0.6 or
+                       alignment[T-1] > 0.6); else stop with status 2 if t > max_decoder_steps, so a
+                       row that never stops takes h_max_steps[b] + 1 steps and S_cap must be at least
+                       max(h_max_steps) + 1); d_post is (B, S_cap*r, postnet_output_dim). At most 64
+                       rows and 1024 input positions per call. h_status: 1 stop rule, 2 max steps.
+   tts_tacotron1_encoder <- Encoder(embedding(ids)): d_out (B, T_max, 256), zero for t >= h_lens[b]
+   tts_tacotron1_postnet <- last_linear(PostCBHG(dec)) on d_dec (B, M_max, 80), rows valid for
+                       m < h_lens[b]: d_out (B, M_max, postnet_output_dim), zero past the rows */
+int tts_tacotron1_set_tensor(tts_ctx* ctx, const char* name, const float* h_data, const int64_t* shape, int ndim);
+int tts_tacotron1_finalize(tts_ctx* ctx, int num_chars, int r_init, int memory_size, int attn_norm,
+                           int postnet_output_dim);
+int tts_tacotron1_infer(tts_ctx* ctx, const int64_t* d_ids, const int32_t* h_lens, int B, int T_max, int r,
+                        const int32_t* h_max_steps, int S_cap, float* d_dec, float* d_post, float* d_align,
+                        float* d_stop, int32_t* h_steps, int32_t* h_status, void* stream);
+int tts_tacotron1_encoder(tts_ctx* ctx, const int64_t* d_ids, const int32_t* h_lens, int B, int T_max,
+                          float* d_out, void* stream);
+int tts_tacotron1_postnet(tts_ctx* ctx, const float* d_dec, const int32_t* h_lens, int B, int M_max, float* d_out,
+                          void* stream);
+
 /* ---- MultiBand-MelGAN generator ---- */
 int tts_melgan_set_tensor(tts_ctx* ctx, const char* name, const float* h_data, const int64_t* shape, int ndim);
 /* upsample_factors: n_up entries (even), base_channels, num_res_blocks, out_channels (4 with PQMF) */

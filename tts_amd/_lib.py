@@ -51,6 +51,13 @@ SIGNATURES = [
     ("tts_taco_encoder", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, _vp, _vp]),
     ("tts_taco_postnet", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, _vp, _vp]),
     ("tts_taco_decoder_state", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("tts_tacotron1_set_tensor", ctypes.c_int, [_vp, ctypes.c_char_p, _vp, _c_i64_p, ctypes.c_int]),
+    ("tts_tacotron1_finalize", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_int]),
+    ("tts_tacotron1_infer", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_int_p,
+                                           ctypes.c_int, _vp, _vp, _vp, _vp, _c_int_p, _c_int_p, _vp]),
+    ("tts_tacotron1_encoder", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, _vp, _vp]),
+    ("tts_tacotron1_postnet", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, _vp, _vp]),
     ("tts_melgan_set_tensor", ctypes.c_int, [_vp, ctypes.c_char_p, _vp, _c_i64_p, ctypes.c_int]),
     ("tts_melgan_finalize", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_int_p, ctypes.c_int,
                                            ctypes.c_int, ctypes.c_int]),
@@ -146,6 +153,7 @@ class Engine:
         self.pwgan_key = None
         self.ge2e_key = None
         self.glow_key = None
+        self.tacotron1_key = None
 
     def close(self):
         if self.h:
@@ -273,6 +281,35 @@ class Engine:
                 raise RuntimeError("decoder_state: another Tacotron2 model decoded on this device since this model's call")
             _check(self.lib.tts_taco_decoder_state(self.h, B, T_max, *[_ptr(out[k]) for k in out], _stream(device)))
         return out
+
+    def load_tacotron1(self, tensors: Dict[str, np.ndarray], num_chars, r_init, memory_size, attn_norm,
+                       postnet_output_dim):
+        for k, v in tensors.items():
+            self._set(self.lib.tts_tacotron1_set_tensor, k, v)
+        _check(self.lib.tts_tacotron1_finalize(self.h, num_chars, r_init, memory_size,
+                                               1 if attn_norm == "softmax" else 0, postnet_output_dim))
+
+    def tacotron1_infer(self, ids, lens, r, max_steps, S_cap, dec, post, align, stop):
+        """Batched Tacotron.inference (tts_tacotron1_infer); S_cap > max(max_steps)."""
+        B, T = ids.shape
+        lens_a, lens_p = _i32(lens)
+        ms_a, ms_p = _i32(max_steps)
+        steps = np.zeros(B, np.int32)
+        status = np.zeros(B, np.int32)
+        _check(self.lib.tts_tacotron1_infer(self.h, _ptr(ids), lens_p, B, T, r, ms_p, S_cap, _ptr(dec), _ptr(post),
+                                            _ptr(align), _ptr(stop), steps.ctypes.data_as(_c_int_p),
+                                            status.ctypes.data_as(_c_int_p), _stream(ids.device)))
+        return steps, status
+
+    def tacotron1_encoder(self, ids, lens, out):
+        B, T = ids.shape
+        lens_a, lens_p = _i32(lens)
+        _check(self.lib.tts_tacotron1_encoder(self.h, _ptr(ids), lens_p, B, T, _ptr(out), _stream(ids.device)))
+
+    def tacotron1_postnet(self, dec, lens, out):
+        B, M, _ = dec.shape
+        lens_a, lens_p = _i32(lens)
+        _check(self.lib.tts_tacotron1_postnet(self.h, _ptr(dec), lens_p, B, M, _ptr(out), _stream(dec.device)))
 
     def load_pwgan(self, tensors: Dict[str, np.ndarray], num_res_blocks, stacks, upsample_factors):
         for k, v in tensors.items():

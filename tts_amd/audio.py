@@ -309,6 +309,35 @@ class AudioProcessor:
             return scipy.signal.lfilter([1], [1, -self.preemphasis], self._griffin_lim(S ** self.power, rng))
         return self._griffin_lim(S ** self.power, rng)
 
+    def inv_spectrogram(self, spectrogram, rng=None):
+        """audio.py:232-239: a normalised linear spectrogram (fft_size / 2 + 1, M) -> waveform:
+        denormalise, dB to amplitude, power, Griffin-Lim, inverse pre-emphasis if configured. With
+        ``griffin_lim_device == "gpu"`` the phase reconstruction runs on the library's batched
+        Griffin-Lim at B = 1 (fp32), behind the same parameter checks as the mel path."""
+        S = self._db_to_amp(self._denormalize(np.asarray(spectrogram))) ** self.power
+        if self.griffin_lim_device == "gpu":
+            from ._lib import get_engine
+            self._gl_check_params()
+            F, M = S.shape
+            if F != self.fft_size // 2 + 1:
+                raise ValueError(f"inv_spectrogram: {F} frequency bins, expected {self.fft_size // 2 + 1}")
+            u = torch.rand(1, M, F) if rng is None else torch.from_numpy(np.ascontiguousarray(
+                np.asarray(rng.rand(F, M), np.float32).T)[None])
+            Sd = torch.from_numpy(np.ascontiguousarray(S.T, dtype=np.float32)[None]).cuda()
+            phase = u.float().cuda().contiguous()
+            out = torch.empty(1, self.hop_length * (M - 1), device=Sd.device)
+            eng = get_engine(Sd.device)
+            with eng.lock:
+                eng.griffin_lim(Sd, [M], self.fft_size, self.win_length, self.hop_length, self.griffin_lim_iters,
+                                phase, out)
+            wav = out[0].cpu().numpy()
+        else:
+            wav = self._griffin_lim(S, rng)
+        if self.preemphasis != 0:
+            import scipy.signal
+            return scipy.signal.lfilter([1], [1, -self.preemphasis], wav)
+        return wav
+
     # -- batched Griffin-Lim on the GPU (tts_mel_to_linear + tts_griffin_lim)
     def _denorm_affine(self):
         """`_denormalize` on a mel as dB = clip(x) * scale + offset per channel: (scale, offset, clip)

@@ -327,6 +327,29 @@ struct PwganWS {
   DevBuf lens, ca, cb, xa, xb, skip, zeros;
 };
 
+// Tacotron v1 (TTS/tts/models/tacotron.py; api_tacotron1.hip, tacotron1.hip): CBHG encoder, GRU
+// decoder, CBHG postnet + last_linear. Conv weights are [K][Cin][Cout] with their BatchNorm folded,
+// linear and GRU matrices transposed ([in][out]) except the sequence GRU's W_hh ([dir][384][128]).
+struct T1Cbhg {
+  int Cin = 0, K = 0, P0 = 0, P1 = 0;
+  std::vector<DevBuf> bank_w, bank_b;
+  DevBuf pj1_w, pj1_b, pj2_w, pj2_b, pre_hw, hw_w, hw_b, gru_wih, gru_bih, gru_whh, gru_bhh;
+};
+
+struct T1Model {
+  bool ready = false;
+  int num_chars = 0, r_init = 5, mem_frames = 5, softmax = 0, post_dim = 1025;
+  DevBuf emb, epre1_w, epre1_b, epre2_w, epre2_b;
+  T1Cbhg enc, post;
+  DevBuf pre1, pre1_b, pre2, pre2_b, att_ih, att_hh, att_bih, att_bhh, wq, win, wcomb, v, pdi, pdi_b;
+  DevBuf rnn_ih[2], rnn_hh[2], rnn_bih[2], rnn_bhh[2], mel, mel_b, stop_w, last_w, last_b;
+  float bv = 0.f, stop_b = 0.f;
+};
+
+struct T1WS {
+  DevBuf lens, msteps, ctl, x0, x1, x2, bank, p1, p2, hw, gin, enc, pin, gout;
+};
+
 // Griffin-Lim (griffin_lim.hip): twiddles, the window of the last call's win_length, the two
 // ping-pong frame buffers (B, M_max, 1024) and the rows' window-square envelopes
 struct AudioWS {
@@ -383,6 +406,9 @@ struct tts_ctx {
   ttsh::GlowModel glow;
   ttsh::GlowWS glws;
   ttsh::AudioWS aws;
+  ttsh::HostMap t1_host;
+  ttsh::T1Model t1;
+  ttsh::T1WS t1ws;
   // last decode configuration (for tts_time_decoder_kernel)
   int last_B = 0, last_T = 0, last_S = 0, last_r = 0;
   // fused Tacotron2 + MB-MelGAN submissions whose vocoder may still run (tts_taco_mbmelgan_submit)

@@ -54,6 +54,49 @@ void launch_pw_out(const float* skip, float scale, const float* W3, const float*
                    const float* b4, const int* lens, int len_add, int hop, int Tmax, float* out, int B,
                    hipStream_t st);
 
+// tacotron1.hip. Activations are channel-last (B, T, C) fp32; every kernel masks by the rows' own
+// lengths (device ints) and writes zeros past them inside [0, T_max).
+constexpr int T1_MEM_MAX = 32;   // memory_size (frames of the decoder's memory queue)
+constexpr int T1_R_MAX = 10;     // r_init
+constexpr int T1_T_MAX = 1024;   // encoder positions the decoder's attention state holds
+// out[b][t][oc0 + co] = act(bias[co] + sum_{k, ci} W[k][ci][co] x[b][t + k - padl][ci]) (+ resid);
+// W is [K][Cin][Cout], act 1 = ReLU, bias / resid may be null; K <= 16
+struct T1Conv {
+  const float* x;
+  long xb;  // batch stride (elements)
+  int ldx, Cin;
+  const float* W;
+  const float* bias;
+  int K, padl, Cout, act;
+  const float* resid;
+  long rb;
+  int ldr;
+  float* out;
+  long ob;
+  int ldo, oc0;
+};
+void launch_t1_conv(const T1Conv& c, const int* lens, int B, int T_max, hipStream_t s);
+// 4 highway layers in place on (B, T_max, 128); Wt [layer][H | T][in][out], bias [layer][H | T][128]
+void launch_t1_highway(float* x, long xb, const float* Wt, const float* bias, const int* lens, int B, int T_max,
+                       hipStream_t s);
+// gin (B, T_max, 768) = [dir][r | z | n] input projections with b_ih; Whh [dir][384][128]; out (B, T_max, 256)
+void launch_t1_bigru(const float* gin, long gb, const float* Whh, const float* bhh, const int* lens, int B, int T_max,
+                     float* out, long ob, hipStream_t s);
+// the whole decode, one workgroup per row. Matrices are transposed ([in][out]); wcomb = location_dense
+// . location_conv folded, [2 channels][31 taps][128]. mem_frames = memory_size (<= 0: last frame only).
+struct T1DecArgs {
+  const float *enc, *pin;  // (B, T_max, 256) encoder outputs, (B, T_max, 128) inputs_layer(enc)
+  const int *lens, *max_steps;
+  int T_max, S_cap, r, r_init, mem_frames, softmax;
+  const float *pre1, *pre1_b, *pre2, *pre2_b, *att_ih, *att_hh, *att_bih, *att_bhh, *wq, *wcomb, *v;
+  float bv;
+  const float *pdi, *pdi_b, *rnn_ih[2], *rnn_hh[2], *rnn_bih[2], *rnn_bhh[2], *mel, *mel_b, *stop_w;
+  float stop_b;
+  float *dec, *align, *stop;   // (B, S_cap * r, 80), (B, S_cap, T_max), (B, S_cap); zeroed by the caller
+  int *steps, *status, *mlens;  // per row: steps taken, 1 = stop rule / 2 = max steps, steps * r
+};
+void launch_t1_decoder(const T1DecArgs& a, int B, hipStream_t s);
+
 // griffin_lim.hip. Row lengths travel as a kernel argument (at most 64 rows), so a call needs no
 // host-to-device copy. W = e^{-2 pi i m / 1024} (1024 complex), win = the window zero-padded to
 // 1024, nonzero inside [wlo, whi); env (B, env_stride) the rows' window-square envelopes; F

@@ -443,3 +443,103 @@ def pwgan_spec(c: PwganConfig, weight_norm: bool = True) -> Spec:
     conv("last_conv_layers.1", (S, S, 1), True)
     conv("last_conv_layers.3", (1, S, 1), True)
     return s
+
+
+@dataclass
+class TacotronV1Config:
+    """Architecture knobs of ``Tacotron(...)`` (``TTS/tts/models/tacotron.py:10-93``,
+    ``TTS/tts/layers/tacotron.py``) that change tensor shapes or math: CBHG encoder (K = 16) on a
+    256-wide embedding, GRU decoder with query size 256, CBHG postnet (K = 8) and ``last_linear``."""
+    num_chars: int = 129
+    r: int = 5                      # r_init: width of proj_to_mel = 80 * r
+    frame_channels: int = 80
+    postnet_output_dim: int = 1025
+    memory_size: int = 5            # <= 0: the decoder prenet reads the last frame only
+    attn_norm: str = "sigmoid"      # 'sigmoid' | 'softmax'
+    double_decoder_consistency: bool = False
+    ddc_r: int = 5
+    bidirectional_decoder: bool = False
+
+    @property
+    def prenet_in(self) -> int:
+        return self.frame_channels * (self.memory_size if self.memory_size > 0 else 1)
+
+
+def _gru(prefix: str, sfx: str, H: int, din: int) -> Spec:
+    return [(f"{prefix}.weight_ih{sfx}", (3 * H, din), "gru"), (f"{prefix}.weight_hh{sfx}", (3 * H, H), "gru"),
+            (f"{prefix}.bias_ih{sfx}", (3 * H,), "gru"), (f"{prefix}.bias_hh{sfx}", (3 * H,), "gru")]
+
+
+def _bnconv(prefix: str, cin: int, cout: int, k: int) -> Spec:
+    return [(f"{prefix}.conv1d.weight", (cout, cin, k), "conv"),
+            (f"{prefix}.bn.weight", (cout,), "bn_w"), (f"{prefix}.bn.bias", (cout,), "bn_b"),
+            (f"{prefix}.bn.running_mean", (cout,), "bn_mean"), (f"{prefix}.bn.running_var", (cout,), "bn_var"),
+            (f"{prefix}.bn.num_batches_tracked", (), "count")]
+
+
+def _cbhg(prefix: str, cin: int, K: int, proj: Tuple[int, int]) -> Spec:
+    s: Spec = []
+    for k in range(1, K + 1):
+        s += _bnconv(f"{prefix}.conv1d_banks.{k - 1}", cin, 128, k)
+    s += _bnconv(f"{prefix}.conv1d_projections.0", 128 * K, proj[0], 3)
+    s += _bnconv(f"{prefix}.conv1d_projections.1", proj[0], proj[1], 3)
+    if proj[1] != 128:
+        s.append((f"{prefix}.pre_highway.weight", (128, proj[1]), "linear"))
+    for i in range(4):
+        s += [(f"{prefix}.highways.{i}.H.weight", (128, 128), "linear_relu"),
+              (f"{prefix}.highways.{i}.H.bias", (128,), "bias"),
+              (f"{prefix}.highways.{i}.T.weight", (128, 128), "linear_sigmoid"),
+              (f"{prefix}.highways.{i}.T.bias", (128,), "highway_gate_bias")]
+    for sfx in ("_l0", "_l0_reverse"):
+        s += _gru(f"{prefix}.gru", sfx, 128, 128)
+    return s
+
+
+def _decoder_v1(prefix: str, c: TacotronV1Config, r: int) -> Spec:
+    F = c.frame_channels
+    s: Spec = [
+        (f"{prefix}.prenet.linear_layers.0.linear_layer.weight", (256, c.prenet_in), "linear_relu"),
+        (f"{prefix}.prenet.linear_layers.0.linear_layer.bias", (256,), "bias"),
+        (f"{prefix}.prenet.linear_layers.1.linear_layer.weight", (128, 256), "linear_relu"),
+        (f"{prefix}.prenet.linear_layers.1.linear_layer.bias", (128,), "bias"),
+    ]
+    s += _gru(f"{prefix}.attention_rnn", "", 256, 128 + 256)
+    s += [
+        (f"{prefix}.attention.query_layer.linear_layer.weight", (128, 256), "linear_tanh"),
+        (f"{prefix}.attention.inputs_layer.linear_layer.weight", (128, 256), "linear_tanh"),
+        (f"{prefix}.attention.v.linear_layer.weight", (1, 128), "attn_v"),
+        (f"{prefix}.attention.v.linear_layer.bias", (1,), "bias"),
+        (f"{prefix}.attention.location_layer.location_conv1d.weight", (32, 2, 31), "conv"),
+        (f"{prefix}.attention.location_layer.location_dense.linear_layer.weight", (128, 32), "linear_tanh"),
+        (f"{prefix}.project_to_decoder_in.weight", (256, 512), "linear"),
+        (f"{prefix}.project_to_decoder_in.bias", (256,), "bias"),
+    ]
+    for i in range(2):
+        s += _gru(f"{prefix}.decoder_rnns.{i}", "", 256, 256)
+    s += [
+        (f"{prefix}.proj_to_mel.weight", (F * r, 256), "linear"),
+        (f"{prefix}.proj_to_mel.bias", (F * r,), "bias"),
+        (f"{prefix}.stopnet.linear.weight", (1, 256 + F * r), "stop_w"),
+        (f"{prefix}.stopnet.linear.bias", (1,), "stop_bias"),
+    ]
+    return s
+
+
+def tacotron_spec(c: TacotronV1Config) -> Spec:
+    """Ordered state_dict spec of the single-speaker ``Tacotron`` without GST: 252 entries for the
+    default model (``tests/golden/tacotron1_keys.json`` holds the reference's own list)."""
+    s: Spec = [("embedding.weight", (c.num_chars, 256), "embedding"),
+               ("encoder.prenet.linear_layers.0.linear_layer.weight", (256, 256), "linear_relu"),
+               ("encoder.prenet.linear_layers.0.linear_layer.bias", (256,), "bias"),
+               ("encoder.prenet.linear_layers.1.linear_layer.weight", (128, 256), "linear_relu"),
+               ("encoder.prenet.linear_layers.1.linear_layer.bias", (128,), "bias")]
+    s += _cbhg("encoder.cbhg.cbhg", 128, 16, (128, 128))
+    s += _decoder_v1("decoder", c, c.r)
+    s += _cbhg("postnet.cbhg", c.frame_channels, 8, (256, c.frame_channels))
+    s += [("last_linear.weight", (c.postnet_output_dim, 256), "linear"),
+          ("last_linear.bias", (c.postnet_output_dim,), "bias")]
+    if c.bidirectional_decoder:  # tacotron_abstract.py:104-105 (deepcopy of the decoder)
+        s += _decoder_v1("decoder_backward", c, c.r)
+    if c.double_decoder_consistency:
+        s += _decoder_v1("coarse_decoder", c, c.ddc_r)
+    return s

@@ -2,7 +2,7 @@
 
 ``synthesis(model, text, CONFIG, use_cuda, ap, ...)`` returns what the reference returns
 (``wav, alignment, decoder_output, postnet_output, stop_tokens, inputs``, ``synthesis.py:178-262``)
-for ``tts_amd`` Tacotron2 and GlowTts models; the model call is ``run_model_torch``
+for ``tts_amd`` Tacotron, Tacotron2 and GlowTts models; the model call is ``run_model_torch``
 (``:48-67``). Host glue only: the model runs in ``libttship.so``; Griffin-Lim (``use_griffin_lim``)
 is the CPU fallback of ``tts_amd.audio``. The TF / TFLite backends are outside this build.
 """

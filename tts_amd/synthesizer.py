@@ -28,6 +28,7 @@ from .audio import AudioProcessor, wav_bytes
 from .factories import load_config, setup_generator, setup_model
 from .glow_tts import GlowTts
 from .multigpu import GpuPool
+from .tacotron import Tacotron
 from .vocoder import MultibandMelganGenerator
 from .text import make_symbols, phonemes, split_into_sentences, symbols, text_to_seqvec
 
@@ -148,6 +149,15 @@ class Synthesizer:
             else:
                 spk = None if speaker_id is None else torch.full((len(seqs),), int(speaker_id), dtype=torch.long)
                 ids = torch.from_numpy(batch).to(dev)
+                if isinstance(self.tts_model, Tacotron):
+                    # linear spectrograms (fft_size / 2 + 1 bins): Griffin-Lim only, as in synthesis.py:83-86
+                    if self.vocoder_model is not None:
+                        raise ValueError("a Tacotron (v1) model outputs linear spectrograms; the vocoders take mels")
+                    _, post, _, _ = self.tts_model.inference(ids, text_lengths=lens)
+                    mel_lens = [int(m) for m in self.tts_model.last_mel_lengths]
+                    post = post.cpu().numpy()
+                    return [self.ap.inv_spectrogram(post[i, :mel_lens[i]].T).astype(np.float32)
+                            for i in range(len(seqs))]
                 if isinstance(self.vocoder_model, MultibandMelganGenerator):
                     # both models in one library call (tts_taco_mbmelgan_infer), same waveforms
                     _, post, _, _, wav = self.tts_model.inference_vocoded(ids, self.vocoder_model, text_lengths=lens,

@@ -37,7 +37,7 @@ def splitmix64_uniform(key: int, n: int) -> np.ndarray:
 
 
 _GAIN = {"linear": 1.0, "linear_relu": math.sqrt(2.0), "linear_tanh": 5.0 / 3.0,
-         "linear_sigmoid": 1.0, "attn_v": 1.0}
+         "linear_sigmoid": 1.0, "attn_v": 1.0, "stop_w": 1.0}
 
 
 def _fans(shape: Tuple[int, ...]) -> Tuple[int, int]:
@@ -70,6 +70,11 @@ def synth_tensor(name: str, shape: Tuple[int, ...], kind: str, seed: int,
     elif kind in ("lstm", "lstm_enc"):
         H = shape[0] // 4
         x = u / math.sqrt(H)
+    elif kind == "gru":  # nn.GRU / nn.GRUCell: U(-1/sqrt(H), 1/sqrt(H)), three gates
+        H = shape[0] // 3
+        x = u / math.sqrt(H)
+    elif kind == "highway_gate_bias":  # Highway.T.bias is filled with -1 (layers/tacotron.py:87)
+        x = -1.0 + 0.05 * u
     elif kind == "xavier":  # xavier_normal_ in the reference (speaker_encoder/model.py:49-54): same std
         fi, fo = _fans(shape)
         x = u * math.sqrt(3.0) * math.sqrt(2.0 / (fi + fo))
