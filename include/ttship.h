@@ -29,6 +29,8 @@
  *                                    (the vocoder still running), completed by finish
  *   tts_mel_to_linear / tts_griffin_lim <- AudioProcessor.inv_melspectrogram on a batch
  *                                    (TTS/utils/audio.py:213-214, 241-248, 259-279)
+ *   tts_stft_mag / tts_mag_to_feature <- AudioProcessor.spectrogram / melspectrogram on a batch of
+ *                                    waveforms (TTS/utils/audio.py:108-124, 198-230, 259-267)
  *
  * Conventions: every function returns 0 on success and nonzero on failure; the message is
  * available from tts_last_error() (thread-local). Pointers prefixed d_ are device (HIP) memory
@@ -278,6 +280,44 @@ int tts_mel_to_linear(tts_ctx* ctx, const float* d_mel, const int32_t* h_lens, i
    the context's queued work before the upload). */
 int tts_griffin_lim(tts_ctx* ctx, const float* d_S, const int32_t* h_lens, int B, int M_max, int n_fft,
                     int win_length, int hop_length, int iters, const float* d_phase0, float* d_wav, void* stream);
+
+/* ---- Audio analysis (TTS/utils/audio.py: waveform -> spectrogram / melspectrogram) ----
+   Both entries only enqueue kernels, as the Griffin-Lim entries above.
+
+   tts_stft_mag <- abs(AudioProcessor._stft(apply_preemphasis(y))) (audio.py:198-202, 259-267) on a
+                       batch: librosa.stft conventions (periodic Hann window of win_length points
+                       centred in n_fft, centred frames, reflect padding), pre-emphasis
+                       y[q] - preemphasis * y[q-1] (y[-1] = 0) applied before the padding; fp32.
+   d_wav       (B, L_max) waveform rows; row b is read for q < h_nsamples[b] only
+   d_mag       (B, M_max, n_fft / 2 + 1) magnitudes, frame-major; row b holds
+               1 + h_nsamples[b] / hop_length frames, the rest of the row is written as zero
+   algo        0: the 1024-point FFT kernel when n_fft == 1024, else a direct DFT over an n_fft-entry
+               twiddle table; 1: the FFT kernel (n_fft == 1024 only); 2: the direct DFT
+   Supported: n_fft even in [64, 2048], 1 <= win_length <= n_fft, 16 <= hop_length <= n_fft,
+   1 <= B <= 64, and every row n_fft / 2 < h_nsamples[b] <= L_max (the reflect padding's own
+   requirement, as torch.stft) with 1 + h_nsamples[b] / hop_length <= M_max. Anything else is an
+   error and launches nothing. Row b equals its own B = 1 call bit for bit. The twiddle and window
+   tables are computed in double on the host, the twiddles once per n_fft (a change of n_fft or
+   win_length waits for the context's queued work before the upload). */
+int tts_stft_mag(tts_ctx* ctx, const float* d_wav, const int32_t* h_nsamples, int B, int L_max, int n_fft,
+                 int win_length, int hop_length, float preemphasis, int algo, float* d_mag, int M_max,
+                 void* stream);
+
+/* tts_mag_to_feature <- AudioProcessor._normalize(_amp_to_db(basis @ mag)) (audio.py:108-124, 205-207):
+                       out = clip(spec_gain * log10(max(1e-5, X)) * scale + offset), X = basis @ mag,
+                       or X = mag when d_basis is NULL (the linear spectrogram; n_out == n_freq)
+   d_mag       (B, M_max, n_freq) magnitudes, frame-major (tts_stft_mag's output); row b is read for
+               t < h_lens[b] only (0 <= h_lens[b] <= M_max)
+   d_basis     (n_out, n_freq) mel filterbank, or NULL
+   d_scale, d_offset (n_out) the normalisation per channel: covers both range normalisations (one
+               value repeated), the mean-var scaler (1 / std, -mean / std) and none (1, 0);
+               use_clip != 0 clips the result to [clip_lo, clip_hi] (clip_norm)
+   d_out       (B, M_max, n_out); frames t >= h_lens[b] are written as zero
+   1 <= B <= 64, 1 <= n_freq, n_out <= 1025. */
+int tts_mag_to_feature(tts_ctx* ctx, const float* d_mag, const int32_t* h_lens, int B, int M_max, int n_freq,
+                       int n_out, const float* d_basis, float spec_gain, const float* d_scale,
+                       const float* d_offset, float clip_lo, float clip_hi, int use_clip, float* d_out,
+                       void* stream);
 
 /* Measurement hook for bench.py: average device time (ms) of `iters` launches of one kernel of the
    last tts_taco_infer configuration, timed with hipEvents on the context's stream.

@@ -93,6 +93,11 @@ SIGNATURES = [
                                          ctypes.c_float, _vp, _vp]),
     ("tts_griffin_lim", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                        ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
+    ("tts_stft_mag", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                    ctypes.c_int, ctypes.c_float, ctypes.c_int, _vp, ctypes.c_int, _vp]),
+    ("tts_mag_to_feature", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          _vp, ctypes.c_float, _vp, _vp, ctypes.c_float, ctypes.c_float, ctypes.c_int,
+                                          _vp, _vp]),
 ]
 
 
@@ -397,6 +402,27 @@ class Engine:
         lens_a, lens_p = _i32(lens)
         _check(self.lib.tts_griffin_lim(self.h, _ptr(S), lens_p, B, M, int(n_fft), int(win_length), int(hop_length),
                                         int(iters), _ptr(phase0), _ptr(wav), _stream(S.device)))
+
+    def stft_mag(self, wav, nsamples, n_fft, win_length, hop_length, preemphasis, mag, algo=0):
+        """Batched STFT magnitudes (tts_stft_mag): ``wav`` (B, L_max) with ``nsamples[b]`` valid
+        samples per row -> ``mag`` (B, M_max, n_fft / 2 + 1), row b zero past 1 + nsamples[b] //
+        hop_length frames. ``algo``: 0 auto, 1 the 1024-point FFT kernel, 2 the direct DFT."""
+        B, L = wav.shape
+        n_a, n_p = _i32(nsamples)
+        _check(self.lib.tts_stft_mag(self.h, _ptr(wav), n_p, B, L, int(n_fft), int(win_length), int(hop_length),
+                                     float(preemphasis), int(algo), _ptr(mag), mag.shape[1], _stream(wav.device)))
+
+    def mag_to_feature(self, mag, lens, basis, spec_gain, scale, offset, clip, out):
+        """Magnitudes (B, M, n_freq) -> normalised dB features ``out`` (B, M, n_out)
+        (tts_mag_to_feature); ``basis`` (n_out, n_freq) or None (linear spectrogram), ``clip`` None
+        or the (lo, hi) bounds applied to the result."""
+        B, M, n_freq = mag.shape
+        lens_a, lens_p = _i32(lens)
+        lo, hi = (0.0, 0.0) if clip is None else clip
+        _check(self.lib.tts_mag_to_feature(self.h, _ptr(mag), lens_p, B, M, n_freq, out.shape[-1],
+                                           None if basis is None else _ptr(basis), float(spec_gain), _ptr(scale),
+                                           _ptr(offset), float(lo), float(hi), int(clip is not None), _ptr(out),
+                                           _stream(mag.device)))
 
     def decoder_stats(self):
         """(path, [(ms, steps) per persistent launch]) of the last Tacotron2 decode."""

@@ -6,7 +6,9 @@ config's pad mode), trimming is librosa.effects.trim's frame-RMS rule. Mean-var 
 audio.py:80-86,108-186) reads compute_statistics.py's stats file through a restricted loader
 (`load_stats_file`). By default none of these touch the GPU; the audio-config key
 ``griffin_lim_device: "gpu"`` moves `inv_melspectrogram` onto the library's batched Griffin-Lim
-kernels (`inv_melspectrogram_batch`, fp32), everything else stays on the host. Parity of the restated librosa pieces is unpinned
+kernels (`inv_melspectrogram_batch`, fp32), and ``analysis_device: "gpu"`` moves `spectrogram` /
+`melspectrogram` onto its analysis kernels (`spectrogram_batch` / `melspectrogram_batch`, fp32);
+everything else stays on the host. Parity of the restated librosa pieces is unpinned
 (librosa is not importable here to make fixtures); tests check their defining properties.
 """
 import io
@@ -137,12 +139,18 @@ class AudioProcessor:
                  power=None, preemphasis=0.0, signal_norm=None, symmetric_norm=None, max_norm=None,
                  mel_fmin=None, mel_fmax=None, spec_gain=20, stft_pad_mode="reflect", clip_norm=True,
                  griffin_lim_iters=None, do_trim_silence=False, trim_db=60, stats_path=None, griffin_lim_device=None,
-                 **_):
+                 analysis_device=None, **_):
         if griffin_lim_device not in (None, "cpu", "gpu"):
             raise ValueError(f"griffin_lim_device must be 'cpu' or 'gpu', got {griffin_lim_device!r}")
+        if analysis_device not in (None, "cpu", "gpu"):
+            raise ValueError(f"analysis_device must be 'cpu' or 'gpu', got {analysis_device!r}")
         # None / "cpu": Griffin-Lim on the host (float64); "gpu": the library's batched kernels (fp32)
         self.griffin_lim_device = griffin_lim_device
         self._gl_dev_cache = {}
+        # None / "cpu": spectrogram / melspectrogram on the host (float64); "gpu": the batched
+        # analysis kernels at B = 1 (fp32)
+        self.analysis_device = analysis_device
+        self._an_dev_cache = {}
         self.sample_rate = sample_rate
         self.num_mels = num_mels
         self.min_level_db = min_level_db or 0
@@ -278,12 +286,90 @@ class AudioProcessor:
         return self._stft(y)
 
     def spectrogram(self, y):
-        """audio.py:216-222."""
+        """audio.py:216-222. With ``analysis_device == "gpu"`` the batched GPU path runs at B = 1
+        (fp32) and the (fft_size / 2 + 1, M) result comes back as numpy."""
+        if self.analysis_device == "gpu":
+            return self._analysis_single(y, mel=False)
         return self._normalize(self._amp_to_db(np.abs(self._preemph_stft(y))))
 
     def melspectrogram(self, y):
-        """audio.py:224-230."""
+        """audio.py:224-230. With ``analysis_device == "gpu"``: as `spectrogram`, (num_mels, M)."""
+        if self.analysis_device == "gpu":
+            return self._analysis_single(y, mel=True)
         return self._normalize(self._amp_to_db(self.mel_basis @ np.abs(self._preemph_stft(y))))
+
+    # -- batched analysis on the GPU (tts_stft_mag + tts_mag_to_feature)
+    def _norm_affine(self, n_channels):
+        """`_normalize` on a dB feature of ``n_channels`` rows as clip(dB * scale + offset) per
+        channel: (scale, offset, clip) with clip None or the (lo, hi) bounds. The inverse of
+        `_denorm_affine`; with mean-var stats the scaler is picked as `_scaler_for` picks it."""
+        ones = np.ones(n_channels)
+        if not self.signal_norm:
+            return ones, 0.0 * ones, None
+        if hasattr(self, "mel_scaler"):
+            sc = self._scaler_for(np.empty((n_channels, 0)))
+            std, mean = np.asarray(sc.scale_, np.float64), np.asarray(sc.mean_, np.float64)
+            return 1.0 / std, -mean / std, None
+        span = -self.min_level_db
+        base = (-self.ref_level_db - self.min_level_db) / span
+        if self.symmetric_norm:
+            scale, offset = 2 * self.max_norm / span, 2 * self.max_norm * base - self.max_norm
+            clip = (-self.max_norm, self.max_norm) if self.clip_norm else None
+        else:
+            scale, offset = self.max_norm / span, self.max_norm * base
+            clip = (0.0, self.max_norm) if self.clip_norm else None
+        return scale * ones, offset * ones, clip
+
+    def _analysis_check_params(self):
+        """What the GPU analysis covers (include/ttship.h, tts_stft_mag)."""
+        if self.stft_pad_mode != "reflect":
+            raise NotImplementedError(f"GPU analysis: stft_pad_mode={self.stft_pad_mode!r} (only 'reflect')")
+        if self.fft_size % 2 or not 64 <= self.fft_size <= 2048:
+            raise NotImplementedError(f"GPU analysis: fft_size={self.fft_size} (even, 64 to 2048)")
+        if not 16 <= self.hop_length <= self.fft_size:
+            raise NotImplementedError(f"GPU analysis: hop_length={self.hop_length} (16 to fft_size)")
+
+    def _analysis_batch(self, wavs, lengths, mel):
+        from ._lib import get_engine
+        self._analysis_check_params()
+        n_freq = self.fft_size // 2 + 1
+        n_out = self.num_mels if mel else n_freq
+        dev = wavs.device
+        eng = get_engine(dev)
+        key = (dev, mel)
+        if key not in self._an_dev_cache:
+            scale, offset, clip = self._norm_affine(n_out)
+            put = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)  # noqa: E731
+            self._an_dev_cache[key] = (put(self.mel_basis) if mel else None, put(scale), put(offset), clip)
+        basis, scale, offset, clip = self._an_dev_cache[key]
+        wavs = wavs.contiguous().float()
+        B = wavs.shape[0]
+        lengths = [int(n) for n in lengths]
+        assert wavs.dim() == 2 and len(lengths) == B
+        frames = [1 + n // self.hop_length for n in lengths]
+        M = max(frames)
+        mag = torch.empty(B, M, n_freq, device=dev)
+        out = torch.empty(B, M, n_out, device=dev)
+        with eng.lock:
+            eng.stft_mag(wavs, lengths, self.fft_size, self.win_length, self.hop_length, self.preemphasis, mag)
+            eng.mag_to_feature(mag, frames, basis, self.spec_gain, scale, offset, clip, out)
+        return out, frames
+
+    def spectrogram_batch(self, wavs, lengths):
+        """`spectrogram` of a batch on the GPU: ``wavs`` (B, L_max) waveform rows on a ROCm device,
+        row b valid for ``lengths[b]`` samples (more than fft_size / 2 each). Returns the
+        (B, M_max, fft_size / 2 + 1) frame-major device tensor (rows zero past their own frame count)
+        and the per-row frame counts 1 + lengths[b] // hop_length."""
+        return self._analysis_batch(wavs, lengths, mel=False)
+
+    def melspectrogram_batch(self, wavs, lengths):
+        """`melspectrogram` of a batch on the GPU; as `spectrogram_batch`, (B, M_max, num_mels)."""
+        return self._analysis_batch(wavs, lengths, mel=True)
+
+    def _analysis_single(self, y, mel):
+        y = np.ascontiguousarray(y, dtype=np.float32)
+        out, frames = self._analysis_batch(torch.from_numpy(y[None]).cuda(), [y.shape[0]], mel)
+        return np.ascontiguousarray(out[0, :frames[0]].cpu().numpy().T)
 
     def inv_melspectrogram(self, mel, rng=None):
         """audio.py:241-248 (no pre-emphasis path: raise as the reference would need scipy lfilter).

@@ -1,5 +1,6 @@
 // Audio post-processing entry points: mel -> linear magnitudes and batched Griffin-Lim
-// (griffin_lim.hip). Both only enqueue work: no host synchronisation, no graph capture.
+// (griffin_lim.hip), and the analysis direction, waveform -> STFT magnitudes -> normalised features
+// (stft.hip). All of them only enqueue work: no host synchronisation, no graph capture.
 #include "host.h"
 
 #include <cmath>
@@ -49,9 +50,82 @@ void gl_tables(tts_ctx* c, int win_length) {
   A.win_length = win_length;
 }
 
+// the analysis side's tables: twiddles e^{-2 pi i m / n_fft} (uploaded once per n_fft) and the
+// periodic Hann window of win_length points centred in n_fft; computed in double
+void stft_tables(tts_ctx* c, int n_fft, int win_length) {
+  AudioWS& A = c->aws;
+  if (A.s_nfft == n_fft && A.s_win == win_length) return;
+  HIP_OK(hipStreamSynchronize(c->s));  // a queued call may still read the previous tables
+  if (A.s_nfft != n_fft) {
+    std::vector<float> W(2 * (size_t)n_fft);
+    for (int m = 0; m < n_fft; ++m) {
+      W[2 * m] = (float)std::cos(-2.0 * M_PI * m / n_fft);
+      W[2 * m + 1] = (float)std::sin(-2.0 * M_PI * m / n_fft);
+    }
+    A.s_nfft = A.s_win = -1;
+    A.sW.upload(W);
+  }
+  std::vector<float> win(n_fft, 0.f);
+  const int lo = (n_fft - win_length) / 2;
+  for (int n = 0; n < win_length; ++n) win[lo + n] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * n / win_length));
+  A.swin.upload(win);
+  A.s_nfft = n_fft;
+  A.s_win = win_length;
+}
+
 }  // namespace
 
 extern "C" {
+
+int tts_stft_mag(tts_ctx* c, const float* d_wav, const int32_t* h_nsamples, int B, int L_max, int n_fft,
+                 int win_length, int hop_length, float preemphasis, int algo, float* d_mag, int M_max, void* stream) {
+  return async_call(
+      c, stream,
+      [&] {
+        TTS_CHECK(d_wav && h_nsamples && d_mag, "null argument");
+        TTS_CHECK(B >= 1 && B <= BMAX, "stft_mag: 1 <= B <= 64");
+        TTS_CHECK(n_fft >= 64 && n_fft <= 2048 && n_fft % 2 == 0, "stft_mag: n_fft must be even and in [64, 2048]");
+        TTS_CHECK(win_length >= 1 && win_length <= n_fft, "stft_mag: win_length outside [1, n_fft]");
+        TTS_CHECK(hop_length >= 16 && hop_length <= n_fft, "stft_mag: hop_length outside [16, n_fft]");
+        TTS_CHECK(algo >= 0 && algo <= 2, "stft_mag: algo must be 0 (auto), 1 (FFT) or 2 (direct)");
+        TTS_CHECK(algo != 1 || n_fft == 1024, "stft_mag: algo 1 (FFT) needs n_fft == 1024");
+        TTS_CHECK(std::isfinite(preemphasis), "stft_mag: preemphasis must be finite");
+        TTS_CHECK(L_max >= 1 && L_max < (1 << 30) && M_max >= 1, "stft_mag: L_max or M_max out of range");
+        for (int b = 0; b < B; ++b)
+          TTS_CHECK(h_nsamples[b] > n_fft / 2 && h_nsamples[b] <= L_max && 1 + h_nsamples[b] / hop_length <= M_max,
+                    "stft_mag: every row needs n_fft / 2 < h_nsamples[b] <= L_max (the reflect padding of "
+                    "torch.stft) and 1 + h_nsamples[b] / hop_length <= M_max");
+      },
+      [&] {
+        AudioWS& A = c->aws;
+        stft_tables(c, n_fft, win_length);
+        const int wlo = (n_fft - win_length) / 2, whi = wlo + win_length;
+        launch_stft_frames(n_fft == 1024 && algo != 2, d_wav, L_max, lens_arg(h_nsamples, B), B, M_max, n_fft,
+                           hop_length, wlo, whi, preemphasis, A.sW.f(), A.swin.f(), d_mag, c->s);
+      });
+}
+
+int tts_mag_to_feature(tts_ctx* c, const float* d_mag, const int32_t* h_lens, int B, int M_max, int n_freq, int n_out,
+                       const float* d_basis, float spec_gain, const float* d_scale, const float* d_offset,
+                       float clip_lo, float clip_hi, int use_clip, float* d_out, void* stream) {
+  return async_call(
+      c, stream,
+      [&] {
+        TTS_CHECK(d_mag && h_lens && d_scale && d_offset && d_out, "null argument");
+        TTS_CHECK(B >= 1 && B <= BMAX, "mag_to_feature: 1 <= B <= 64");
+        TTS_CHECK(M_max >= 1, "mag_to_feature: M_max must be positive");
+        TTS_CHECK(n_freq >= 1 && n_freq <= 1025, "mag_to_feature: 1 <= n_freq <= 1025");
+        TTS_CHECK(n_out >= 1 && n_out <= 1025, "mag_to_feature: 1 <= n_out <= 1025");
+        TTS_CHECK(d_basis || n_out == n_freq, "mag_to_feature: without a basis n_out must equal n_freq");
+        for (int b = 0; b < B; ++b)
+          TTS_CHECK(h_lens[b] >= 0 && h_lens[b] <= M_max, "mag_to_feature: h_lens[b] outside [0, M_max]");
+      },
+      [&] {
+        launch_mag_to_feature(d_mag, lens_arg(h_lens, B), B, M_max, n_freq, n_out, d_basis, spec_gain, d_scale,
+                              d_offset, clip_lo, clip_hi, use_clip, d_out, c->s);
+      });
+}
+
 
 int tts_mel_to_linear(tts_ctx* c, const float* d_mel, const int32_t* h_lens, int B, int M_max, int n_mels, int n_freq,
                       const float* d_inv_basis, const float* d_scale, const float* d_offset, float clip_lo,

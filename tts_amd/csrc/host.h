@@ -355,6 +355,9 @@ struct T1WS {
 struct AudioWS {
   DevBuf W, win, fa, fb, env;
   int win_length = -1;
+  // analysis (stft.hip): twiddles e^{-2 pi i m / n_fft} and the window of the last tts_stft_mag call
+  DevBuf sW, swin;
+  int s_nfft = -1, s_win = -1;
 };
 
 // one submitted fused call: what its fp32 re-run needs if the split-f16 vocoder raised the range

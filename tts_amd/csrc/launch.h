@@ -114,3 +114,14 @@ void launch_gl_finish(const float* F, const float* env, float* wav, const GlLens
 void launch_mel_to_linear(const float* mel, const GlLens& lens, int B, int M_max, int n_mels, int F, const float* inv,
                           const float* scale, const float* offset, float clip_lo, float clip_hi, int use_clip,
                           float spec_gain, float power, float* S, hipStream_t s);
+
+// stft.hip. nsamp holds the rows' sample counts (by value, as above); W = e^{-2 pi i m / n_fft}
+// (n_fft complex), win = the window zero-padded to n_fft, nonzero inside [wlo, whi). fft: the
+// 1024-point FFT kernel (n_fft must be 1024), else the direct DFT. out (B, M_max, n_fft / 2 + 1).
+void launch_stft_frames(bool fft, const float* wav, long L_max, const GlLens& nsamp, int B, int M_max, int n_fft,
+                        int hop, int wlo, int whi, float preemph, const float* W, const float* win, float* out,
+                        hipStream_t s);
+// mag (B, M_max, F) -> out (B, M_max, C); basis (C, F) or null (then C == F)
+void launch_mag_to_feature(const float* mag, const GlLens& lens, int B, int M_max, int F, int C, const float* basis,
+                           float gain, const float* scale, const float* offset, float clip_lo, float clip_hi,
+                           int use_clip, float* out, hipStream_t s);

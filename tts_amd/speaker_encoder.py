@@ -9,6 +9,9 @@ call (each window is its own sequence with its own length), not one call per win
 
 Batching (new, optional): ``inference`` takes per-sequence ``lengths``; row b's embedding is taken
 at frame ``lengths[b] - 1`` and equals the reference run on ``x[b:b+1, :lengths[b]]``.
+``compute_embedding_batch`` is ``compute_embedding`` for B utterances at once (the counterpart of
+``batch_compute_embedding``, ``:91-111``, with every utterance cut by its own length), and
+``embed_utterances`` starts from device waveforms.
 """
 
 from typing import Optional, Sequence
@@ -102,3 +105,45 @@ class SpeakerEncoder(nn.Module):
             batch[i, :e - o] = x[0, o:e]
         emb = self.inference(batch, lengths=[e - o for o, e in wins])
         return (emb.sum(0, keepdim=True) / len(wins))
+
+    @staticmethod
+    def embedding_windows(T, num_frames=160, overlap=0.5):
+        """The (offset, end) frame windows `compute_embedding` cuts from T frames (model.py:72-89)."""
+        num_overlap = int(num_frames * overlap)
+        return [(o, min(T, o + num_frames)) for o in range(0, T, num_frames - num_overlap)]
+
+    @torch.no_grad()
+    def compute_embedding_batch(self, mels, lengths, num_frames=160, overlap=0.5):
+        """`compute_embedding` of B utterances at once: ``mels`` (B, T_max, D) frame-major, row b
+        valid for ``lengths[b]`` frames. The windows of every utterance (ragged at each tail) are
+        packed into as few library calls as MAX_SEQS allows, and the per-utterance means are taken
+        on the device. Returns (B, proj_dim), usable as ``Tacotron2.inference(speaker_embeddings=)``."""
+        dev = self._device()
+        mels = torch.as_tensor(mels).to(dev, torch.float32)
+        B, T_max, D = mels.shape
+        lengths = [int(n) for n in lengths]
+        if len(lengths) != B or min(lengths) < 1 or max(lengths) > T_max:
+            raise ValueError("lengths must have B entries in [1, T_max]")
+        wins = [(b, o, e) for b, n in enumerate(lengths) for o, e in self.embedding_windows(n, num_frames, overlap)]
+        L = max(e - o for _, o, e in wins)
+        # one gather builds every window: frame t of window w is mels[b_w, o_w + t], clamped into the
+        # row (frames past a window's own length are never read by the library)
+        row = torch.tensor([b for b, _, _ in wins], device=dev)
+        off = torch.tensor([o for _, o, _ in wins], device=dev)
+        t = (off[:, None] + torch.arange(L, device=dev)[None, :]).clamp_(max=T_max - 1)
+        batch = mels[row[:, None], t]
+        emb = self.inference(batch, lengths=[e - o for _, o, e in wins])
+        # an utterance's windows are consecutive rows of emb: its mean as compute_embedding takes it
+        counts = [sum(1 for b2, _, _ in wins if b2 == b) for b in range(B)]
+        out, w0 = torch.empty(B, self.cfg.proj_dim, device=dev), 0
+        for b, n in enumerate(counts):
+            out[b] = emb[w0:w0 + n].sum(0) / n
+            w0 += n
+        return out
+
+    @torch.no_grad()
+    def embed_utterances(self, wavs, lengths, ap):
+        """Waveforms (B, L_max) on the device, ``lengths[b]`` samples each -> (B, proj_dim)
+        embeddings: ``ap.melspectrogram_batch`` then `compute_embedding_batch`, no host copy between."""
+        mels, frames = ap.melspectrogram_batch(wavs, lengths)
+        return self.compute_embedding_batch(mels, frames)
