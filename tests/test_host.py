@@ -267,11 +267,14 @@ class _FakeTacoEngine:
     def __init__(self):
         import threading
         self.lock = threading.RLock()
-        self.taco_key = None
+        self.weight_keys = {}
         self.calls = []
+        self.max_steps_rows = None  # rows per call that report status 2 (None: all of them)
 
     def load_tacotron(self, *a, **k):
         pass
+
+    load_tacotron1 = load_tacotron
 
     def taco_infer(self, ids, lens, r, ms, S_cap, thr, dec, post, align, stop, speaker_ids=None,
                    speaker_embeddings=None):
@@ -286,48 +289,106 @@ class _FakeTacoEngine:
             post[i, :steps[i] * r] = tag + 0.5
             align[i, :steps[i], :int(lens[i])] = tag
             stop[i, :steps[i]] = tag
-        return steps, np.full(nb, 2, np.int32)
+        k = nb if self.max_steps_rows is None else self.max_steps_rows
+        return steps, np.where(np.arange(nb) < k, 2, 1).astype(np.int32)
+
+    def tacotron1_infer(self, ids, lens, r, ms, S_cap, dec, post, align, stop):
+        return self.taco_infer(ids, lens, r, ms, S_cap, None, dec, post, align, stop)
+
+
+def _fake_engine(monkeypatch):
+    """Every model finds its engine through tts_amd._lib.get_engine, looked up at call time."""
+    eng = _FakeTacoEngine()
+    monkeypatch.setattr("tts_amd._lib.get_engine", lambda dev: eng)
+    return eng
+
+
+def _ragged_batch(rs, B, long_row):
+    """B padded rows tagged i + 1 with random lengths and step counts; ``long_row`` decodes longest."""
+    lens = rs.randint(1, 30, B)
+    steps = rs.randint(1, 6, B)
+    steps[long_row] = 17
+    ids = np.zeros((B, lens.max()), np.int64)
+    for i in range(B):
+        ids[i, :lens[i]] = i + 1
+    return ids, lens, steps
+
+
+def _check_joined_rows(outs, lens, steps, r):
+    dec, post, align, stop = outs
+    for i in range(len(lens)):
+        M = r * steps[i]
+        assert (dec[i, :M] == i + 1).all() and not dec[i, M:].any()
+        assert (post[i, :M] == i + 1.5).all() and not post[i, M:].any()
+        assert (align[i, :steps[i], :lens[i]] == i + 1).all() and not align[i, :, lens[i]:].any()
+        assert not align[i, steps[i]:].any() and not stop[i, steps[i]:].any()
 
 
 def test_tacotron2_multichunk_join_ragged_steps(monkeypatch):
     """B = 70 splits into chunks of 64 and 6 that decode to different S_cap (the second chunk
     longer than the first, then shorter): every row keeps its own frames and zero padding, in
     the caller's order (the join used to assume equal chunk lengths)."""
-    import tts_amd.tacotron2 as tmod
-    eng = _FakeTacoEngine()
-    monkeypatch.setattr(tmod, "get_engine", lambda dev: eng)
+    eng = _fake_engine(monkeypatch)
     m = Tacotron2(num_chars=129, r=7, attn_norm="sigmoid")
     m.decoder.set_r(2)
     m.decoder.verbose = False
     B = 70
     rs = np.random.RandomState(0)
     for long_chunk in (0, 1):
-        lens = rs.randint(1, 30, B)
-        steps = rs.randint(1, 6, B)
-        steps[64 + 2 if long_chunk else 5] = 17  # the longest row sits in one chunk only
-        ids = np.zeros((B, lens.max()), np.int64)
-        for i in range(B):
-            ids[i, :lens[i]] = i + 1
+        ids, lens, steps = _ragged_batch(rs, B, 64 + 2 if long_chunk else 5)  # the longest row sits in one chunk only
         eng.calls.clear()
         dec, post, align, stop = m.inference(torch.from_numpy(ids), text_lengths=lens, max_decoder_steps=steps)
         assert [c[0] for c in eng.calls] == [64, 6]
         S = int(steps.max())
         assert dec.shape == (B, 2 * S, 80) and post.shape == (B, 2 * S, 80)
         assert align.shape == (B, S, lens.max()) and stop.shape == (B, S, 1)
-        for i in range(B):
-            M = 2 * steps[i]
-            assert (dec[i, :M] == i + 1).all() and not dec[i, M:].any()
-            assert (post[i, :M] == i + 1.5).all() and not post[i, M:].any()
-            assert (align[i, :steps[i], :lens[i]] == i + 1).all() and not align[i, :, lens[i]:].any()
-            assert not align[i, steps[i]:].any() and not stop[i, steps[i]:].any()
+        _check_joined_rows((dec, post, align, stop), lens, steps, 2)
         assert list(m.last_steps) == list(steps)
+
+
+def test_tacotron1_multichunk_join_ragged_steps(monkeypatch):
+    """The same 64 + 6 split through Tacotron (v1): each library call gets S_cap = its rows' largest
+    max_decoder_steps + 1, and the join keeps every row's own frames and zero padding."""
+    from tts_amd import Tacotron
+    eng = _fake_engine(monkeypatch)
+    m = Tacotron(num_chars=129, num_speakers=0, r=5, postnet_output_dim=33)
+    m.decoder.set_r(2)
+    m.decoder.verbose = False
+    B = 70
+    rs = np.random.RandomState(0)
+    for long_chunk in (0, 1):
+        ids, lens, steps = _ragged_batch(rs, B, 64 + 2 if long_chunk else 5)
+        eng.calls.clear()
+        dec, post, align, stop = m.inference(torch.from_numpy(ids), text_lengths=lens, max_decoder_steps=steps)
+        assert eng.calls == [(64, int(steps[:64].max()) + 1, int(lens[:64].max())),
+                             (6, int(steps[64:].max()) + 1, int(lens[64:].max()))]
+        S = int(steps.max())
+        assert dec.shape == (B, 2 * S, 80) and post.shape == (B, 2 * S, 33)
+        assert align.shape == (B, S, lens.max()) and stop.shape == (B, S, 1)
+        _check_joined_rows((dec, post, align, stop), lens, steps, 2)
+        assert list(m.last_steps) == list(steps) and list(m.last_mel_lengths) == list(2 * steps)
+
+
+@pytest.mark.parametrize("v1", [False, True])
+def test_decoder_stop_line_is_printed_once_per_row_at_max_steps(monkeypatch, capsys, v1):
+    """layers/tacotron2.py:365, layers/tacotron.py:493: one line per row that ran into
+    max_decoder_steps, unless ``decoder.verbose`` is False."""
+    from tts_amd import Tacotron
+    eng = _fake_engine(monkeypatch)
+    m = Tacotron(num_chars=129, num_speakers=0, postnet_output_dim=33) if v1 else Tacotron2(num_chars=129, r=2)
+    ids = torch.ones(5, 4, dtype=torch.long)
+    eng.max_steps_rows = 3
+    m.inference(ids, max_decoder_steps=2)
+    assert capsys.readouterr().out == "   | > Decoder stopped with 'max_decoder_steps\n" * 3
+    assert list(m.last_status) == [2, 2, 2, 1, 1]
+    m.decoder.verbose = False
+    m.inference(ids, max_decoder_steps=2)
+    assert capsys.readouterr().out == ""
 
 
 def test_single_speaker_model_ignores_speaker_arguments(monkeypatch):
     """models/tacotron2.py:152: speaker_ids / speaker_embeddings are ignored when num_speakers <= 1."""
-    import tts_amd.tacotron2 as tmod
-    eng = _FakeTacoEngine()
-    monkeypatch.setattr(tmod, "get_engine", lambda dev: eng)
+    _fake_engine(monkeypatch)
     m = Tacotron2(num_chars=129, r=2, attn_norm="sigmoid")
     m.decoder.verbose = False
     ids = torch.ones(1, 5, dtype=torch.long)
@@ -336,6 +397,127 @@ def test_single_speaker_model_ignores_speaker_arguments(monkeypatch):
                     max_decoder_steps=3)
     for x, y in zip(a, b):
         assert torch.equal(x, y)
+
+
+class _RecordingEngine:
+    """Records every ``load_*`` call as (method, tensor names, finalize arguments)."""
+
+    def __init__(self):
+        self.weight_keys = {}
+        self.loads = []
+        self.fail = False
+
+    def __getattr__(self, name):
+        if not name.startswith("load_"):
+            raise AttributeError(name)
+
+        def load(tensors, *args):
+            if self.fail:  # as the library: the old weights are gone by the time finalize throws
+                raise RuntimeError("ttship: model not finalized")
+            self.loads.append((name, list(tensors), args))
+        return load
+
+
+def _sync_cases():
+    from tts_amd import (FullbandMelganGenerator, GlowTts, MelganGenerator, ParallelWaveganGenerator, SpeakerEncoder,
+                         Tacotron)
+    taco = ("coarse_decoder.", "decoder_backward.")
+    pqmf = ("pqmf_layer.H", "pqmf_layer.updown")
+    # name: (constructor, slot, load method, skipped state_dict prefixes, finalize arguments)
+    return {
+        "tacotron2": (lambda: Tacotron2(num_chars=129, r=7, attn_norm="sigmoid", double_decoder_consistency=True,
+                                        ddc_r=7), "taco", "load_tacotron", taco,
+                      (129, 7, "sigmoid", False, False, False)),
+        "tacotron": (lambda: Tacotron(num_chars=129, num_speakers=0), "tacotron1", "load_tacotron1", taco,
+                     (129, 5, 5, "sigmoid", 1025)),
+        "melgan": (MelganGenerator, "melgan", "load_melgan", pqmf, (80, 1, 512, (8, 8, 2, 2), 3, False)),
+        "multiband_melgan": (lambda: MultibandMelganGenerator(upsample_factors=(8, 4, 2), num_res_blocks=4),
+                             "melgan", "load_melgan", pqmf, (80, 4, 384, (8, 4, 2), 4, True)),
+        "fullband_melgan": (FullbandMelganGenerator, "melgan", "load_melgan", pqmf,
+                            (80, 1, 512, (2, 8, 2, 2), 4, False)),
+        "pwgan": (ParallelWaveganGenerator, "pwgan", "load_pwgan", (), (30, 3, (4, 4, 4, 4))),
+        "ge2e": (lambda: SpeakerEncoder(input_dim=40), "ge2e", "load_ge2e", (), (40, 256, 768, 3, True)),
+        "glow": (lambda: GlowTts(num_chars=130), "glow", "load_glow", (), (130, 9, 12, 4)),
+    }
+
+
+SYNC_CASES = ["tacotron2", "tacotron", "melgan", "multiband_melgan", "fullband_melgan", "pwgan", "ge2e", "glow"]
+
+
+@pytest.mark.parametrize("case", SYNC_CASES)
+def test_sync_loads_once_per_weight_change(case):
+    """``_sync`` uploads exactly when the engine's slot holds another model or another version of
+    this one: what is uploaded (names, finalize arguments) and every event that bumps the version."""
+    from tts_amd.params import host_tensors
+    make, slot, method, skip, final = _sync_cases()[case]
+    eng, m = _RecordingEngine(), make()
+    m._sync(eng)
+    assert len(eng.loads) == 1
+    name, names, args = eng.loads[0]
+    assert name == method and args == final
+    assert names == list(host_tensors(m, skip_prefixes=skip))
+    assert not any(n.startswith(p) for n in names for p in skip)
+    if case == "tacotron2":
+        assert any(k.startswith("coarse_decoder.") for k in m.state_dict())
+    if case == "multiband_melgan":
+        assert "pqmf_layer.H" in m.state_dict() and "pqmf_layer.G" in names
+    m._sync(eng)
+    assert len(eng.loads) == 1
+    bumps = [m.invalidate, lambda: m.load_state_dict(m.state_dict()), m.float]
+    if hasattr(m, "remove_weight_norm"):
+        bumps.append(m.remove_weight_norm)
+    for n, bump in enumerate(bumps, 2):
+        bump()
+        m._sync(eng)
+        assert len(eng.loads) == n
+        m._sync(eng)
+        assert len(eng.loads) == n
+    if hasattr(m, "remove_weight_norm"):
+        assert not any(k.endswith(("weight_g", "weight_v")) for k in eng.loads[-1][1])
+    other = make()
+    for n, model in enumerate((other, m, other, m), len(eng.loads) + 1):
+        model._sync(eng)
+        assert len(eng.loads) == n
+    assert eng.weight_keys == {slot: m.weight_key}
+
+
+def test_melgan_family_shares_one_slot():
+    from tts_amd import FullbandMelganGenerator, MelganGenerator
+    eng = _RecordingEngine()
+    models = [MelganGenerator(), MultibandMelganGenerator(upsample_factors=(8, 4, 2), num_res_blocks=4),
+              FullbandMelganGenerator()]
+    for n, m in enumerate(models + models, 1):
+        m._sync(eng)
+        assert len(eng.loads) == n and eng.weight_keys == {"melgan": m.weight_key}
+
+
+@pytest.mark.parametrize("case", SYNC_CASES)
+def test_failed_load_empties_the_slot(case):
+    """The library drops a slot's weights before a load can fail, so the model that held the slot
+    must upload again afterwards instead of finding its old key there."""
+    make, slot = _sync_cases()[case][:2]
+    eng, a, b = _RecordingEngine(), make(), make()
+    a._sync(eng)
+    eng.fail = True
+    with pytest.raises(RuntimeError, match="not finalized"):
+        b._sync(eng)
+    assert eng.weight_keys[slot] is None
+    eng.fail = False
+    a._sync(eng)
+    assert len(eng.loads) == 2 and eng.weight_keys[slot] == a.weight_key
+
+
+@pytest.mark.parametrize("case", SYNC_CASES)
+def test_reload_counter_stays_out_of_saved_checkpoints(case):
+    """state_dict()._metadata carries nn.Module._version, torch's format version of the module; the
+    models' reload counter must not shadow it."""
+    m = _sync_cases()[case][0]()
+    before = m.weight_key
+    m.invalidate()
+    m.invalidate()
+    assert m.weight_key == (before[0], before[1] + 2)
+    assert m.state_dict()._metadata[""]["version"] == torch.nn.Module._version
+    assert "_version" not in vars(m)
 
 
 def test_runtime_switch_table_matches_switches_header():

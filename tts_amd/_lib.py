@@ -133,6 +133,10 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _opt_ptr(t):
+    return None if t is None else _ptr(t)
+
+
 def _stream(device):
     import torch
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
@@ -153,12 +157,7 @@ class Engine:
         h = ctypes.c_void_p()
         _check(self.lib.tts_ctx_create(device_index, ctypes.byref(h)))
         self.h = h
-        self.taco_key = None
-        self.melgan_key = None
-        self.pwgan_key = None
-        self.ge2e_key = None
-        self.glow_key = None
-        self.tacotron1_key = None
+        self.weight_keys = {}  # weight slot -> (token, version) of the model whose weights it holds
 
     def close(self):
         if self.h:
@@ -171,59 +170,56 @@ class Engine:
         shape = (ctypes.c_int64 * max(1, a.ndim))(*a.shape)
         _check(fn(self.h, name.encode(), a.ctypes.data_as(ctypes.c_void_p), shape, a.ndim))
 
+    def _load_model(self, prefix, tensors, *finalize_args):
+        set_tensor = getattr(self.lib, f"tts_{prefix}_set_tensor")
+        for k, v in tensors.items():
+            self._set(set_tensor, k, v)
+        _check(getattr(self.lib, f"tts_{prefix}_finalize")(self.h, *finalize_args))
+
     def load_tacotron(self, tensors: Dict[str, np.ndarray], num_chars: int, r_init: int, attn_norm: str,
                       windowing: bool = False, forward_attn: bool = False, forward_attn_mask: bool = False):
         _check(self.lib.tts_taco_set_options(self.h, int(bool(windowing)), int(bool(forward_attn)),
                                              int(bool(forward_attn and forward_attn_mask))))
-        for k, v in tensors.items():
-            self._set(self.lib.tts_taco_set_tensor, k, v)
-        _check(self.lib.tts_taco_finalize(self.h, num_chars, r_init, 1 if attn_norm == "softmax" else 0))
+        self._load_model("taco", tensors, num_chars, r_init, 1 if attn_norm == "softmax" else 0)
 
     def load_melgan(self, tensors: Dict[str, np.ndarray], in_channels, out_channels, base_channels,
                     upsample_factors, num_res_blocks, use_pqmf):
-        for k, v in tensors.items():
-            self._set(self.lib.tts_melgan_set_tensor, k, v)
         ups, ups_p = _i32(list(upsample_factors))
-        _check(self.lib.tts_melgan_finalize(self.h, in_channels, out_channels, base_channels, ups_p, len(ups),
-                                            num_res_blocks, 1 if use_pqmf else 0))
+        self._load_model("melgan", tensors, in_channels, out_channels, base_channels, ups_p, len(ups),
+                         num_res_blocks, 1 if use_pqmf else 0)
 
     # -- compute (device tensors) ----------------------------------------------------
-    def taco_infer(self, ids, lens, r, max_steps, S_cap, stop_threshold, dec, post, align, stop,
-                   speaker_ids=None, speaker_embeddings=None):
+    def _decode_args(self, ids, lens, r, max_steps, S_cap):
+        """What the Tacotron decode entry points share: their leading arguments, the per-row steps /
+        status arrays they fill with the pointers to them, and the host arrays behind the leading
+        pointers (the caller holds on to those until the call has returned)."""
         B, T = ids.shape
         lens_a, lens_p = _i32(lens)
         ms_a, ms_p = _i32(max_steps)
         steps = np.zeros(B, np.int32)
         status = np.zeros(B, np.int32)
+        return ((self.h, _ptr(ids), lens_p, B, T, r, ms_p, S_cap), steps, status,
+                (steps.ctypes.data_as(_c_int_p), status.ctypes.data_as(_c_int_p)), (lens_a, ms_a))
+
+    def taco_infer(self, ids, lens, r, max_steps, S_cap, stop_threshold, dec, post, align, stop,
+                   speaker_ids=None, speaker_embeddings=None):
+        head, steps, status, res, keep = self._decode_args(ids, lens, r, max_steps, S_cap)
+        outs = (_ptr(dec), _ptr(post), _ptr(align), _ptr(stop))
         if speaker_ids is None and speaker_embeddings is None:
-            _check(self.lib.tts_taco_infer(self.h, _ptr(ids), lens_p, B, T, r, ms_p, S_cap, float(stop_threshold),
-                                           _ptr(dec), _ptr(post), _ptr(align), _ptr(stop),
-                                           steps.ctypes.data_as(_c_int_p), status.ctypes.data_as(_c_int_p),
-                                           _stream(ids.device)))
+            _check(self.lib.tts_taco_infer(*head, float(stop_threshold), *outs, *res, _stream(ids.device)))
         else:
-            sid = None if speaker_ids is None else _ptr(speaker_ids)
-            semb = None if speaker_embeddings is None else _ptr(speaker_embeddings)
-            _check(self.lib.tts_taco_infer_spk(self.h, _ptr(ids), lens_p, B, T, r, ms_p, S_cap,
-                                               float(stop_threshold), sid, semb, _ptr(dec), _ptr(post),
-                                               _ptr(align), _ptr(stop), steps.ctypes.data_as(_c_int_p),
-                                               status.ctypes.data_as(_c_int_p), _stream(ids.device)))
+            _check(self.lib.tts_taco_infer_spk(*head, float(stop_threshold), _opt_ptr(speaker_ids),
+                                               _opt_ptr(speaker_embeddings), *outs, *res, _stream(ids.device)))
         return steps, status
 
     def taco_mbmelgan_infer(self, ids, lens, r, max_steps, S_cap, stop_threshold, dec, post, align, stop, pad, wav,
                             speaker_ids=None, speaker_embeddings=None):
         """Tacotron2 decode and MB-MelGAN on its postnet output in one library call
         (tts_taco_mbmelgan_infer); ``wav`` holds B * hop * (S_cap * r + 2 pad) floats."""
-        B, T = ids.shape
-        lens_a, lens_p = _i32(lens)
-        ms_a, ms_p = _i32(max_steps)
-        steps = np.zeros(B, np.int32)
-        status = np.zeros(B, np.int32)
-        sid = None if speaker_ids is None else _ptr(speaker_ids)
-        semb = None if speaker_embeddings is None else _ptr(speaker_embeddings)
-        _check(self.lib.tts_taco_mbmelgan_infer(self.h, _ptr(ids), lens_p, B, T, r, ms_p, S_cap, float(stop_threshold),
-                                                sid, semb, _ptr(dec), _ptr(post), _ptr(align), _ptr(stop), int(pad),
-                                                _ptr(wav), steps.ctypes.data_as(_c_int_p),
-                                                status.ctypes.data_as(_c_int_p), _stream(ids.device)))
+        head, steps, status, res, keep = self._decode_args(ids, lens, r, max_steps, S_cap)
+        _check(self.lib.tts_taco_mbmelgan_infer(*head, float(stop_threshold), _opt_ptr(speaker_ids),
+                                                _opt_ptr(speaker_embeddings), _ptr(dec), _ptr(post), _ptr(align),
+                                                _ptr(stop), int(pad), _ptr(wav), *res, _stream(ids.device)))
         return steps, status
 
     def taco_mbmelgan_submit(self, ids, lens, r, max_steps, S_cap, stop_threshold, dec, post, align, stop, pad, wav,
@@ -231,18 +227,11 @@ class Engine:
         """The first half of taco_mbmelgan_infer (tts_taco_mbmelgan_submit): returns (steps, status,
         ticket) once the decode is done, the vocoder still running; ``post`` and ``wav`` must stay
         untouched until ``taco_mbmelgan_finish(ticket)``."""
-        B, T = ids.shape
-        lens_a, lens_p = _i32(lens)
-        ms_a, ms_p = _i32(max_steps)
-        steps = np.zeros(B, np.int32)
-        status = np.zeros(B, np.int32)
+        head, steps, status, res, keep = self._decode_args(ids, lens, r, max_steps, S_cap)
         ticket = ctypes.c_int64(0)
-        sid = None if speaker_ids is None else _ptr(speaker_ids)
-        semb = None if speaker_embeddings is None else _ptr(speaker_embeddings)
-        _check(self.lib.tts_taco_mbmelgan_submit(self.h, _ptr(ids), lens_p, B, T, r, ms_p, S_cap, float(stop_threshold),
-                                                 sid, semb, _ptr(dec), _ptr(post), _ptr(align), _ptr(stop), int(pad),
-                                                 _ptr(wav), steps.ctypes.data_as(_c_int_p),
-                                                 status.ctypes.data_as(_c_int_p), ctypes.byref(ticket),
+        _check(self.lib.tts_taco_mbmelgan_submit(*head, float(stop_threshold), _opt_ptr(speaker_ids),
+                                                 _opt_ptr(speaker_embeddings), _ptr(dec), _ptr(post), _ptr(align),
+                                                 _ptr(stop), int(pad), _ptr(wav), *res, ctypes.byref(ticket),
                                                  _stream(ids.device)))
         # a fp32 re-run at finish reads post and writes wav: keep them allocated while the library
         # may still do that (it finishes a ticket at the latest when the 5th submission after it
@@ -282,28 +271,21 @@ class Engine:
                 ("decoder_cell", 1024), ("context", 512), ("attention_weights", T_max),
                 ("attention_weights_cum", T_max))}
         with self.lock:
-            if key is not None and self.taco_key != key:
+            if key is not None and self.weight_keys.get("taco") != key:
                 raise RuntimeError("decoder_state: another Tacotron2 model decoded on this device since this model's call")
             _check(self.lib.tts_taco_decoder_state(self.h, B, T_max, *[_ptr(out[k]) for k in out], _stream(device)))
         return out
 
     def load_tacotron1(self, tensors: Dict[str, np.ndarray], num_chars, r_init, memory_size, attn_norm,
                        postnet_output_dim):
-        for k, v in tensors.items():
-            self._set(self.lib.tts_tacotron1_set_tensor, k, v)
-        _check(self.lib.tts_tacotron1_finalize(self.h, num_chars, r_init, memory_size,
-                                               1 if attn_norm == "softmax" else 0, postnet_output_dim))
+        self._load_model("tacotron1", tensors, num_chars, r_init, memory_size, 1 if attn_norm == "softmax" else 0,
+                         postnet_output_dim)
 
     def tacotron1_infer(self, ids, lens, r, max_steps, S_cap, dec, post, align, stop):
         """Batched Tacotron.inference (tts_tacotron1_infer); S_cap > max(max_steps)."""
-        B, T = ids.shape
-        lens_a, lens_p = _i32(lens)
-        ms_a, ms_p = _i32(max_steps)
-        steps = np.zeros(B, np.int32)
-        status = np.zeros(B, np.int32)
-        _check(self.lib.tts_tacotron1_infer(self.h, _ptr(ids), lens_p, B, T, r, ms_p, S_cap, _ptr(dec), _ptr(post),
-                                            _ptr(align), _ptr(stop), steps.ctypes.data_as(_c_int_p),
-                                            status.ctypes.data_as(_c_int_p), _stream(ids.device)))
+        head, steps, status, res, keep = self._decode_args(ids, lens, r, max_steps, S_cap)
+        _check(self.lib.tts_tacotron1_infer(*head, _ptr(dec), _ptr(post), _ptr(align), _ptr(stop), *res,
+                                            _stream(ids.device)))
         return steps, status
 
     def tacotron1_encoder(self, ids, lens, out):
@@ -317,10 +299,8 @@ class Engine:
         _check(self.lib.tts_tacotron1_postnet(self.h, _ptr(dec), lens_p, B, M, _ptr(out), _stream(dec.device)))
 
     def load_pwgan(self, tensors: Dict[str, np.ndarray], num_res_blocks, stacks, upsample_factors):
-        for k, v in tensors.items():
-            self._set(self.lib.tts_pwgan_set_tensor, k, v)
         ups, ups_p = _i32(list(upsample_factors))
-        _check(self.lib.tts_pwgan_finalize(self.h, num_res_blocks, stacks, ups_p, len(ups)))
+        self._load_model("pwgan", tensors, num_res_blocks, stacks, ups_p, len(ups))
 
     def pwgan_infer(self, mel, lens, pad, noise, out):
         B, _, M = mel.shape
@@ -329,9 +309,7 @@ class Engine:
                                         _stream(mel.device)))
 
     def load_glow(self, tensors: Dict[str, np.ndarray], num_chars, enc_layers, flows, wn_layers):
-        for k, v in tensors.items():
-            self._set(self.lib.tts_glow_set_tensor, k, v)
-        _check(self.lib.tts_glow_finalize(self.h, num_chars, enc_layers, flows, wn_layers))
+        self._load_model("glow", tensors, num_chars, enc_layers, flows, wn_layers)
 
     def glow_encode(self, ids, lens, length_scale, speaker_ids=None):
         B, T = ids.shape
@@ -353,9 +331,7 @@ class Engine:
                                         _ptr(attn), _ptr(logw), _stream(y.device)))
 
     def load_ge2e(self, tensors: Dict[str, np.ndarray], input_dim, proj_dim, lstm_dim, num_layers, with_proj):
-        for k, v in tensors.items():
-            self._set(self.lib.tts_ge2e_set_tensor, k, v)
-        _check(self.lib.tts_ge2e_finalize(self.h, input_dim, proj_dim, lstm_dim, num_layers, 1 if with_proj else 0))
+        self._load_model("ge2e", tensors, input_dim, proj_dim, lstm_dim, num_layers, 1 if with_proj else 0)
 
     def ge2e_infer(self, x, lens, out):
         B, T, _ = x.shape

@@ -25,14 +25,14 @@ from typing import Optional
 
 import numpy as np
 import torch
-from torch import nn
 
-from ._lib import get_engine
-from .params import host_tensors, new_token, populate
+from .params import NativeModel, host_tensors, populate, row_lengths
 from .spec import GlowConfig, glow_spec
 
 
-class GlowTts(nn.Module):
+class GlowTts(NativeModel):
+    _slot = "glow"
+
     def __init__(self, num_chars, hidden_channels=192, filter_channels=768, filter_channels_dp=256, out_channels=80,
                  kernel_size=3, num_heads=2, num_layers_enc=6, dropout_p=0.1, num_flow_blocks_dec=12,
                  kernel_size_dec=5, dilation_rate=1, num_block_layers=4, dropout_p_dec=0., num_speakers=0,
@@ -67,21 +67,6 @@ class GlowTts(nn.Module):
         self.noise_scale = 0.66
         self.length_scale = 1.
         populate(self, glow_spec(self.cfg))
-        self._version = 0
-        self._token = new_token()
-
-    def load_state_dict(self, state_dict, strict=True, **kw):
-        res = super().load_state_dict(state_dict, strict=strict, **kw)
-        self._version += 1
-        return res
-
-    def _apply(self, fn, *args, **kwargs):
-        res = super()._apply(fn, *args, **kwargs)
-        self._version += 1
-        return res
-
-    def invalidate(self):
-        self._version += 1
 
     def store_inverse(self):  # the library inverts InvConvNear and folds weight norm at load
         pass
@@ -89,14 +74,10 @@ class GlowTts(nn.Module):
     def forward(self, *args, **kwargs):
         raise NotImplementedError("training forward is out of scope; use inference()")
 
-    def _sync(self, eng):
-        key = (self._token, self._version)
-        if eng.glow_key != key:
-            c = self.cfg
-            enc_layers = c.num_layers_enc if c.encoder_type == "transformer" else 3 + c.num_layers_enc
-            eng.load_glow(host_tensors(self), c.num_chars, enc_layers, c.num_flow_blocks_dec,
-                          c.num_block_layers)
-            eng.glow_key = key
+    def _load(self, eng):
+        c = self.cfg
+        enc_layers = c.num_layers_enc if c.encoder_type == "transformer" else 3 + c.num_layers_enc
+        eng.load_glow(host_tensors(self), c.num_chars, enc_layers, c.num_flow_blocks_dec, c.num_block_layers)
 
     @torch.no_grad()
     def inference(self, x, x_lengths, g=None, noise: Optional[torch.Tensor] = None):
@@ -112,8 +93,8 @@ class GlowTts(nn.Module):
         elif self.cfg.c_in_channels:
             raise RuntimeError(f"the duration predictor expects {192 + self.cfg.c_in_channels} input channels "
                                "(c_in_channels > 0): pass g")
-        dev = self.encoder.emb.weight.device
-        eng = get_engine(dev)
+        dev = self.device
+        eng = self._engine()
         with eng.lock:  # encode and decode share the context's Glow workspace
             self._sync(eng)
             x = torch.as_tensor(x).to(dev, torch.int64)
@@ -121,9 +102,7 @@ class GlowTts(nn.Module):
                 x = x[None]
             x = x.contiguous()
             B, T = x.shape
-            lens = np.asarray(torch.as_tensor(x_lengths).cpu(), np.int64).reshape(-1)
-            if len(lens) != B or lens.min() < 1 or lens.max() > T:
-                raise ValueError("x_lengths must have B entries in [1, T]")
+            lens = row_lengths(torch.as_tensor(x_lengths).reshape(-1), B, T, "x_lengths")
             if B > 64:
                 raise ValueError("at most 64 utterances per call")
             if spk is not None and len(spk) != B:

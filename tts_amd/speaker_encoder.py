@@ -16,18 +16,17 @@ at frame ``lengths[b] - 1`` and equals the reference run on ``x[b:b+1, :lengths[
 
 from typing import Optional, Sequence
 
-import numpy as np
 import torch
-from torch import nn
 
-from ._lib import get_engine
-from .params import host_tensors, new_token, populate
+from .params import NativeModel, host_tensors, populate, row_lengths
 from .spec import Ge2eConfig, ge2e_spec
 
 MAX_SEQS = 64  # sequences per library call
 
 
-class SpeakerEncoder(nn.Module):
+class SpeakerEncoder(NativeModel):
+    _slot = "ge2e"
+
     def __init__(self, input_dim, proj_dim=256, lstm_dim=768, num_lstm_layers=3, use_lstm_with_projection=True):
         super().__init__()
         if lstm_dim != 768:
@@ -36,40 +35,19 @@ class SpeakerEncoder(nn.Module):
         self.cfg = Ge2eConfig(input_dim=input_dim, proj_dim=proj_dim, lstm_dim=lstm_dim,
                               num_lstm_layers=num_lstm_layers, use_lstm_with_projection=use_lstm_with_projection)
         populate(self, ge2e_spec(self.cfg))
-        self._version = 0
-        self._token = new_token()
-
-    def load_state_dict(self, state_dict, strict=True, **kw):
-        res = super().load_state_dict(state_dict, strict=strict, **kw)
-        self._version += 1
-        return res
-
-    def _apply(self, fn, *args, **kwargs):
-        res = super()._apply(fn, *args, **kwargs)
-        self._version += 1
-        return res
-
-    def invalidate(self):
-        self._version += 1
 
     def forward(self, x):
         return self.inference(x)
 
-    def _device(self):
-        return next(self.parameters()).device
-
-    def _sync(self, eng):
-        key = (self._token, self._version)
-        if eng.ge2e_key != key:
-            c = self.cfg
-            eng.load_ge2e(host_tensors(self), c.input_dim, c.proj_dim, c.lstm_dim, c.num_lstm_layers,
-                          c.use_lstm_with_projection)
-            eng.ge2e_key = key
+    def _load(self, eng):
+        c = self.cfg
+        eng.load_ge2e(host_tensors(self), c.input_dim, c.proj_dim, c.lstm_dim, c.num_lstm_layers,
+                      c.use_lstm_with_projection)
 
     @torch.no_grad()
     def inference(self, x, lengths: Optional[Sequence[int]] = None):
-        dev = self._device()
-        eng = get_engine(dev)
+        dev = self.device
+        eng = self._engine()
         x = torch.as_tensor(x).to(dev, torch.float32)
         if x.dim() == 2:
             x = x[None]
@@ -77,9 +55,7 @@ class SpeakerEncoder(nn.Module):
         B, T, D = x.shape
         if D != self.cfg.input_dim:
             raise ValueError(f"expected {self.cfg.input_dim} mel channels, got {D}")
-        lens = np.full(B, T, np.int64) if lengths is None else np.asarray(torch.as_tensor(lengths).cpu(), np.int64)
-        if len(lens) != B or lens.min() < 1 or lens.max() > T:
-            raise ValueError("lengths must have B entries in [1, T]")
+        lens = row_lengths(lengths, B, T, "lengths")
         out = torch.empty(B, self.cfg.proj_dim, device=dev)
         with eng.lock:
             self._sync(eng)
@@ -118,7 +94,7 @@ class SpeakerEncoder(nn.Module):
         valid for ``lengths[b]`` frames. The windows of every utterance (ragged at each tail) are
         packed into as few library calls as MAX_SEQS allows, and the per-utterance means are taken
         on the device. Returns (B, proj_dim), usable as ``Tacotron2.inference(speaker_embeddings=)``."""
-        dev = self._device()
+        dev = self.device
         mels = torch.as_tensor(mels).to(dev, torch.float32)
         B, T_max, D = mels.shape
         lengths = [int(n) for n in lengths]

@@ -21,11 +21,10 @@ from typing import Optional, Sequence
 
 import numpy as np
 import torch
-from torch import nn
 
-from ._lib import get_engine
-from .params import Container, host_tensors, new_token, populate
+from .params import Container, host_tensors, populate
 from .spec import TacotronV1Config, tacotron_spec
+from .tacotron_host import TacotronHost
 
 BATCH_LIMIT = 64  # rows per library call (ttship.h)
 
@@ -47,7 +46,9 @@ class Decoder(Container):
         self.r = int(new_r)
 
 
-class Tacotron(nn.Module):
+class Tacotron(TacotronHost):
+    _slot = "tacotron1"
+
     def __init__(self, num_chars, num_speakers, r=5, postnet_output_dim=1025, decoder_output_dim=80,
                  attn_type="original", attn_win=False, attn_norm="sigmoid", prenet_type="original",
                  prenet_dropout=True, forward_attn=False, trans_agent=False, forward_attn_mask=False,
@@ -103,67 +104,25 @@ class Tacotron(nn.Module):
         order = list(dict.fromkeys(name.split(".")[0] for name, _, _ in spec))
         for k in order:
             self._modules[k] = self._modules.pop(k)
-        self._version = 0
-        self._token = new_token()
-        self.last_steps = None
-        self.last_mel_lengths = None
-        self.last_status = None
 
-    # any change of parameters or placement invalidates the packed device copy
-    def load_state_dict(self, state_dict, strict=True, **kw):
-        res = super().load_state_dict(state_dict, strict=strict, **kw)
-        self._version += 1
-        return res
+    def _load(self, eng):
+        eng.load_tacotron1(host_tensors(self, skip_prefixes=("coarse_decoder.", "decoder_backward.")),
+                           self.num_chars, self.decoder.r_init, self.cfg.memory_size, self.attn_norm,
+                           self.postnet_output_dim)
 
-    def _apply(self, fn, *args, **kwargs):
-        res = super()._apply(fn, *args, **kwargs)
-        self._version += 1
-        return res
-
-    def invalidate(self):
-        """Call after editing parameters in place."""
-        self._version += 1
-
-    def forward(self, *args, **kwargs):
-        raise NotImplementedError("training forward is out of scope; use inference()")
-
-    def _sync(self, eng):
-        key = (self._token, self._version)
-        if eng.tacotron1_key != key:
-            eng.load_tacotron1(host_tensors(self, skip_prefixes=("coarse_decoder.", "decoder_backward.")),
-                               self.num_chars, self.decoder.r_init, self.cfg.memory_size, self.attn_norm,
-                               self.postnet_output_dim)
-            eng.tacotron1_key = key
-
-    def _prepare(self, characters, text_lengths, max_decoder_steps):
-        dev = self.embedding.weight.device
-        eng = get_engine(dev)
-        text = torch.as_tensor(characters).to(dev, torch.int64)
-        if text.dim() == 1:
-            text = text[None]
-        text = text.contiguous()
-        B, T = text.shape
-        lens = np.full(B, T, np.int64) if text_lengths is None else np.asarray(
-            torch.as_tensor(text_lengths).cpu(), dtype=np.int64)
-        if len(lens) != B or lens.min() < 1 or lens.max() > T:
-            raise ValueError("text_lengths must have B entries in [1, T]")
-        ms = self.decoder.max_decoder_steps if max_decoder_steps is None else max_decoder_steps
-        ms = np.broadcast_to(np.asarray(ms, dtype=np.int64), (B,)).copy()
-        if ms.min() < 1:
+    def _text_args(self, characters, text_lengths, max_decoder_steps):
+        args = super()._text_args(characters, text_lengths, max_decoder_steps)
+        if args[4].min() < 1:
             raise ValueError("max_decoder_steps must be >= 1")
-        r = int(self.decoder.r)
-        if not 1 <= r <= self.decoder.r_init:
-            raise ValueError(f"r={r} must be in [1, r_init={self.decoder.r_init}]")
-        return dev, eng, text, lens, ms, r
+        return args
 
     @torch.no_grad()
     def inference(self, characters, speaker_ids=None, style_mel=None, speaker_embeddings=None,
                   text_lengths: Optional[Sequence[int]] = None, max_decoder_steps=None):
         """speaker_ids / style_mel / speaker_embeddings are ignored, as the reference ignores them
         for a single-speaker model without GST (models/tacotron.py:154-166)."""
-        dev, eng, text, lens, ms, r = self._prepare(characters, text_lengths, max_decoder_steps)
+        dev, eng, text, lens, ms, r = self._text_args(characters, text_lengths, max_decoder_steps)
         B = text.shape[0]
-        P = self.postnet_output_dim
         outs = []
         with eng.lock:
             self._sync(eng)
@@ -172,56 +131,16 @@ class Tacotron(nn.Module):
                 Tn = int(lens[b0:b1].max())
                 sub = text[b0:b1, :Tn].contiguous()
                 S_cap = int(ms[b0:b1].max()) + 1  # a row that never stops takes max_decoder_steps + 1 steps
-                nb = b1 - b0
-                dec = torch.empty(nb, S_cap * r, 80, device=dev, dtype=torch.float32)
-                post = torch.empty(nb, S_cap * r, P, device=dev, dtype=torch.float32)
-                align = torch.empty(nb, S_cap, Tn, device=dev, dtype=torch.float32)
-                stop = torch.empty(nb, S_cap, device=dev, dtype=torch.float32)
+                dec, post, align, stop = self._out_tensors(b1 - b0, S_cap, r, Tn, dev)
                 steps, status = eng.tacotron1_infer(sub, lens[b0:b1], r, ms[b0:b1], S_cap, dec, post, align, stop)
                 outs.append((dec, post, align, stop, steps, status))
-        return self._assemble(outs, text.shape, lens, r, dev)
-
-    def _assemble(self, outs, shape, lens, r, dev):
-        B, T = shape
-        P = self.postnet_output_dim
-        steps = np.concatenate([o[4] for o in outs])
-        status = np.concatenate([o[5] for o in outs])
-        if getattr(self.decoder, "verbose", True):  # reference behaviour (layers/tacotron.py:493)
-            for s in status:
-                if s == 2:
-                    print("   | > Decoder stopped with 'max_decoder_steps")
-        S = int(steps.max())
-        M = S * r
-        if len(outs) == 1:
-            dec, post, align, stop = outs[0][0][:, :M], outs[0][1][:, :M], outs[0][2][:, :S], outs[0][3][:, :S]
-            if align.shape[2] != T:
-                align = torch.nn.functional.pad(align, (0, T - align.shape[2]))
-        else:
-            # chunks of a split batch decode to their own S_cap; each is cut or zero-padded to the
-            # batch's S steps before joining (a chunk's rows are zero past their own steps)
-            dec = torch.zeros(B, M, 80, device=dev)
-            post = torch.zeros(B, M, P, device=dev)
-            align = torch.zeros(B, S, T, device=dev)
-            stop = torch.zeros(B, S, device=dev)
-            b0 = 0
-            for o in outs:
-                n, Sc, Tn = o[2].shape
-                s_ = min(S, Sc)
-                dec[b0:b0 + n, :s_ * r] = o[0][:, :s_ * r]
-                post[b0:b0 + n, :s_ * r] = o[1][:, :s_ * r]
-                align[b0:b0 + n, :s_, :Tn] = o[2][:, :s_]
-                stop[b0:b0 + n, :s_] = o[3][:, :s_]
-                b0 += n
-        self.last_steps = steps
-        self.last_mel_lengths = steps * r
-        self.last_status = status
-        return dec, post, align, stop[:, :, None]
+        return self._assemble(outs, text.shape, r, dev)
 
     # stage entry points (parity by stage)
     @torch.no_grad()
     def encode(self, characters, text_lengths=None):
         """Encoder outputs (B, T, 256) = Encoder(embedding(characters)), zero past each row's length."""
-        dev, eng, text, lens, _, _ = self._prepare(characters, text_lengths, None)
+        dev, eng, text, lens, _, _ = self._text_args(characters, text_lengths, None)
         out = torch.empty(text.shape[0], text.shape[1], 256, device=dev, dtype=torch.float32)
         with eng.lock:
             self._sync(eng)
@@ -231,8 +150,8 @@ class Tacotron(nn.Module):
     @torch.no_grad()
     def run_postnet(self, decoder_outputs, mel_lengths=None):
         """last_linear(PostCBHG(decoder_outputs)) on (B, M, 80) frames -> (B, M, postnet_output_dim)."""
-        dev = self.embedding.weight.device
-        eng = get_engine(dev)
+        dev = self.device
+        eng = self._engine()
         dec = torch.as_tensor(decoder_outputs).to(dev, torch.float32).contiguous()
         B, M, _ = dec.shape
         lens = np.full(B, M, np.int64) if mel_lengths is None else np.asarray(mel_lengths, dtype=np.int64)

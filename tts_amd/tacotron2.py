@@ -16,13 +16,11 @@ run B > 1: ``layers/tacotron2.py:362``). Per-utterance lengths are in ``last_ste
 
 from typing import Optional, Sequence
 
-import numpy as np
 import torch
-from torch import nn
 
-from ._lib import get_engine
-from .params import Container, host_tensors, new_token, populate
+from .params import Container, host_tensors, populate
 from .spec import TacotronConfig, tacotron2_spec
+from .tacotron_host import TacotronHost
 
 BATCH_LIMIT = 64
 SPEAKER_BATCH_LIMIT = 64  # multi-speaker / decoder variants run on the persistent decoder (<= 64 rows)
@@ -61,7 +59,9 @@ class VocodedResult:
         return tuple(self.outputs) + (self._wav,)
 
 
-class Tacotron2(nn.Module):
+class Tacotron2(TacotronHost):
+    _slot = "taco"
+
     def __init__(self, num_chars, num_speakers=0, r=7, postnet_output_dim=80, decoder_output_dim=80,
                  attn_type="original", attn_win=False, attn_norm="softmax", prenet_type="original",
                  prenet_dropout=True, forward_attn=False, trans_agent=False, forward_attn_mask=False,
@@ -94,6 +94,7 @@ class Tacotron2(nn.Module):
         self.num_speakers = num_speakers
         self.r = r
         self.attn_norm = attn_norm
+        self.postnet_output_dim = postnet_output_dim
         self.double_decoder_consistency = double_decoder_consistency
         self.cfg = TacotronConfig(num_chars=num_chars, r=r, attn_norm=attn_norm,
                                   double_decoder_consistency=double_decoder_consistency,
@@ -112,11 +113,6 @@ class Tacotron2(nn.Module):
         self.speaker_embedding_dim = self.cfg.spk_dim
         self.decoder = Decoder(r, decoder_output_dim)
         populate(self, tacotron2_spec(self.cfg))
-        self._version = 0
-        self._token = new_token()
-        self.last_steps = None
-        self.last_mel_lengths = None
-        self.last_status = None
 
     def _speaker_args(self, speaker_ids, speaker_embeddings, B, dev):
         """Speaker conditioning as the reference takes it (models/tacotron2.py:152-155): ids into
@@ -143,62 +139,20 @@ class Tacotron2(nn.Module):
             raise IndexError("speaker id out of range")  # nn.Embedding raises too
         return ids.to(dev).contiguous(), None
 
-    # any change of parameters or placement invalidates the packed device copy
-    def load_state_dict(self, state_dict, strict=True, **kw):
-        res = super().load_state_dict(state_dict, strict=strict, **kw)
-        self._version += 1
-        return res
-
-    def _apply(self, fn, *args, **kwargs):
-        res = super()._apply(fn, *args, **kwargs)
-        self._version += 1
-        return res
-
-    def invalidate(self):
-        """Call after editing parameters in place."""
-        self._version += 1
-
-    def forward(self, *args, **kwargs):
-        raise NotImplementedError("training forward is out of scope; use inference()")
-
-    def _sync(self, eng):
-        key = (self._token, self._version)
-        if eng.taco_key != key:
-            eng.load_tacotron(host_tensors(self, skip_prefixes=("coarse_decoder.", "decoder_backward.")), self.num_chars,
-                              self.decoder.r_init, self.attn_norm, self.cfg.windowing, self.cfg.forward_attn,
-                              self.cfg.forward_attn_mask)
-            eng.taco_key = key
+    def _load(self, eng):
+        eng.load_tacotron(host_tensors(self, skip_prefixes=("coarse_decoder.", "decoder_backward.")), self.num_chars,
+                          self.decoder.r_init, self.attn_norm, self.cfg.windowing, self.cfg.forward_attn,
+                          self.cfg.forward_attn_mask)
 
     def _prepare(self, text, speaker_ids, speaker_embeddings, text_lengths, max_decoder_steps):
         """Arguments of one inference call, checked and placed: (device, engine, ids, lengths, per-row
         max steps, r, speaker ids / embeddings, rows per library call)."""
-        dev = self.embedding.weight.device
-        eng = get_engine(dev)
-        text = torch.as_tensor(text).to(dev, torch.int64)
-        if text.dim() == 1:
-            text = text[None]
-        text = text.contiguous()
-        B, T = text.shape
-        lens = np.full(B, T, np.int64) if text_lengths is None else np.asarray(
-            torch.as_tensor(text_lengths).cpu(), dtype=np.int64)
-        if len(lens) != B or lens.min() < 1 or lens.max() > T:
-            raise ValueError("text_lengths must have B entries in [1, T]")
-        ms = self.decoder.max_decoder_steps if max_decoder_steps is None else max_decoder_steps
-        ms = np.broadcast_to(np.asarray(ms, dtype=np.int64), (B,)).copy()
-        r = int(self.decoder.r)
-        if not 1 <= r <= self.decoder.r_init:
-            raise ValueError(f"r={r} must be in [1, r_init={self.decoder.r_init}]")
-        spk_ids, spk_emb = self._speaker_args(speaker_ids, speaker_embeddings, B, dev)
+        dev, eng, text, lens, ms, r = self._text_args(text, text_lengths, max_decoder_steps)
+        spk_ids, spk_emb = self._speaker_args(speaker_ids, speaker_embeddings, text.shape[0], dev)
         variant = self.cfg.prenet_type == "bn" or self.cfg.windowing or self.cfg.forward_attn or \
             self.cfg.attn_type == "graves"
         limit = BATCH_LIMIT if self.num_speakers <= 1 and not variant else SPEAKER_BATCH_LIMIT
         return dev, eng, text, lens, ms, r, spk_ids, spk_emb, limit
-
-    @staticmethod
-    def _out_tensors(nb, S_cap, r, Tn, dev):
-        dec = torch.empty(nb, S_cap * r, 80, device=dev, dtype=torch.float32)
-        return (dec, torch.empty_like(dec), torch.empty(nb, S_cap, Tn, device=dev, dtype=torch.float32),
-                torch.empty(nb, S_cap, device=dev, dtype=torch.float32))
 
     @torch.no_grad()
     def inference(self, text, speaker_ids=None, style_mel=None, speaker_embeddings=None,
@@ -222,45 +176,8 @@ class Tacotron2(nn.Module):
                     speaker_ids=None if spk_ids is None else spk_ids[b0:b1].contiguous(),
                     speaker_embeddings=None if spk_emb is None else spk_emb[b0:b1].contiguous())
                 outs.append((dec, post, align, stop, steps, status))
-        return self._assemble(outs, text.shape, lens, r, dev)
-
-    def _assemble(self, outs, shape, lens, r, dev):
-        """The library calls' outputs as the reference's (B, M, 80) x 2, (B, S, T), (B, S, 1), and the
-        per-row lengths on ``self`` (last_steps, last_mel_lengths, last_status)."""
-        B, T = shape
-        steps = np.concatenate([o[4] for o in outs])
-        status = np.concatenate([o[5] for o in outs])
-        if getattr(self.decoder, "verbose", True):  # reference behaviour (tacotron2.py:365); bench.py mutes it
-            for s in status:
-                if s == 2:
-                    print("   | > Decoder stopped with 'max_decoder_steps")
-        S = int(steps.max())
-        M = S * r
-        if len(outs) == 1:
-            dec, post, align, stop = outs[0][0][:, :M], outs[0][1][:, :M], outs[0][2][:, :S], outs[0][3][:, :S]
-            if align.shape[2] != T:
-                align = torch.nn.functional.pad(align, (0, T - align.shape[2]))
-        else:
-            # chunks of a split batch decode to their own S_cap; each is cut or zero-padded to the
-            # batch's S steps (M frames) before joining (a chunk's rows are zero past their own steps)
-            dec = torch.zeros(B, M, 80, device=dev)
-            post = torch.zeros(B, M, 80, device=dev)
-            align = torch.zeros(B, S, T, device=dev)
-            stop = torch.zeros(B, S, device=dev)
-            b0 = 0
-            for o in outs:
-                n, Sc, Tn = o[2].shape
-                s_ = min(S, Sc)
-                dec[b0:b0 + n, :s_ * r] = o[0][:, :s_ * r]
-                post[b0:b0 + n, :s_ * r] = o[1][:, :s_ * r]
-                align[b0:b0 + n, :s_, :Tn] = o[2][:, :s_]
-                stop[b0:b0 + n, :s_] = o[3][:, :s_]
-                b0 += n
-        self.last_steps = steps
-        self.last_mel_lengths = steps * r
-        self.last_status = status
         self._last_call = (B, int(lens.max()), len(outs))
-        return dec, post, align, stop[:, :, None]
+        return self._assemble(outs, text.shape, r, dev)
 
     @torch.no_grad()
     def inference_vocoded(self, text, vocoder, speaker_ids=None, speaker_embeddings=None,
@@ -291,7 +208,7 @@ class Tacotron2(nn.Module):
         dev, eng, text, lens, ms, r, spk_ids, spk_emb, limit = self._prepare(
             text, speaker_ids, speaker_embeddings, text_lengths, max_decoder_steps)
         B = text.shape[0]
-        vdev = vocoder.layers._modules["1"].bias.device if isinstance(vocoder, MultibandMelganGenerator) else None
+        vdev = vocoder.device if isinstance(vocoder, MultibandMelganGenerator) else None
         if vdev != dev or B > limit or vocoder.cfg.in_channels != 80:
             dec, post, align, stop = self.inference(text, speaker_ids=speaker_ids, speaker_embeddings=speaker_embeddings,
                                                     text_lengths=lens, max_decoder_steps=ms)
@@ -313,7 +230,8 @@ class Tacotron2(nn.Module):
             else:
                 steps, status = eng.taco_mbmelgan_infer(*args, speaker_ids=spk_ids, speaker_embeddings=spk_emb)
                 ticket = None
-        res = self._assemble([(dec, post, align, stop, steps, status)], text.shape, lens, r, dev)
+        self._last_call = (B, Tn, 1)
+        res = self._assemble([(dec, post, align, stop, steps, status)], text.shape, r, dev)
         L = hop * (int(steps.max()) * r + 2 * pad)
         return VocodedResult(res, wbuf[:B * L].view(B, 1, L), eng, ticket)
 
@@ -330,7 +248,4 @@ class Tacotron2(nn.Module):
             raise RuntimeError("run inference first")
         if nchunks != 1:
             raise RuntimeError("decoder_state: the last call was split into several library calls")
-        dev = self.embedding.weight.device
-        eng = get_engine(dev)
-        st = eng.taco_decoder_state(B, T, dev, key=(self._token, self._version))
-        return st
+        return self._engine().taco_decoder_state(B, T, self.device, key=self.weight_key)

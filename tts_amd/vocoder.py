@@ -12,10 +12,9 @@ from typing import Optional, Sequence
 
 import numpy as np
 import torch
-from torch import nn
 
 from ._lib import get_engine
-from .params import Container, host_tensors, new_token, populate
+from .params import Container, NativeModel, host_tensors, populate
 from .pqmf import pqmf_filters
 from .spec import MelganConfig, PwganConfig, melgan_layers, melgan_spec, pwgan_spec
 
@@ -48,7 +47,8 @@ class PQMF(Container):
         raise NotImplementedError("PQMF analysis is training-only and out of scope")
 
 
-class MelganGenerator(nn.Module):
+class MelganGenerator(NativeModel):
+    _slot = "melgan"
     _use_pqmf = False
 
     def __init__(self, in_channels=80, out_channels=1, proj_kernel=7, base_channels=512,
@@ -66,57 +66,26 @@ class MelganGenerator(nn.Module):
         self.inference_padding = 2
         self._wn = True
         populate(self, melgan_spec(self.cfg, weight_norm=True))
-        self._version = 0
-        self._token = new_token()
 
     @property
     def hop(self):
         return int(np.prod(self.cfg.upsample_factors)) * (self.cfg.out_channels if self._use_pqmf else 1)
 
-    def load_state_dict(self, state_dict, strict=True, **kw):
-        res = super().load_state_dict(state_dict, strict=strict, **kw)
-        self._version += 1
-        return res
-
-    def _apply(self, fn, *args, **kwargs):
-        res = super()._apply(fn, *args, **kwargs)
-        self._version += 1
-        return res
-
-    def invalidate(self):
-        self._version += 1
-
     def remove_weight_norm(self):
         """Fold w = g * v / ||v|| (melgan_generator.py:91-97, melgan.py:41-45)."""
-        if not self._wn:
-            return
-        for l in melgan_layers(self.cfg):
-            *path, = l.name.split(".")
-            m = self
-            for p in path:
-                m = m._modules[p]
-            g, v = m.weight_g.data, m.weight_v.data
-            w = torch._weight_norm(v, g, 0)
-            del m._parameters["weight_g"]
-            del m._parameters["weight_v"]
-            m.weight = nn.Parameter(w.contiguous(), requires_grad=False)
-        self._wn = False
-        self._version += 1
+        self._fold_weight_norm(l.name for l in melgan_layers(self.cfg))
 
     def forward(self, c):
         return self.inference(c)
 
-    def _sync(self, eng):
-        key = (self._token, self._version)
-        if eng.melgan_key != key:
-            eng.load_melgan(host_tensors(self, skip_prefixes=("pqmf_layer.H", "pqmf_layer.updown")),
-                            self.cfg.in_channels, self.cfg.out_channels, self.cfg.base_channels,
-                            self.cfg.upsample_factors, self.cfg.num_res_blocks, self._use_pqmf)
-            eng.melgan_key = key
+    def _load(self, eng):
+        eng.load_melgan(host_tensors(self, skip_prefixes=("pqmf_layer.H", "pqmf_layer.updown")),
+                        self.cfg.in_channels, self.cfg.out_channels, self.cfg.base_channels,
+                        self.cfg.upsample_factors, self.cfg.num_res_blocks, self._use_pqmf)
 
     def _prep(self, c, lengths, frame_major_ok=False):
-        dev = self.layers._modules["1"].bias.device
-        eng = get_engine(dev)
+        dev = self.device
+        eng = self._engine()
         c = torch.as_tensor(c).to(dev, torch.float32)
         if c.dim() == 2:
             c = c[None]
@@ -167,7 +136,7 @@ class MultibandMelganGenerator(MelganGenerator):
                          num_res_blocks=num_res_blocks)
         self.pqmf_layer = PQMF(N=4, taps=62, cutoff=0.15, beta=9.0)
         self.cfg.pqmf = True
-        self._version += 1
+        self.invalidate()
 
     def pqmf_synthesis(self, x):
         return self.pqmf_layer.synthesis(x)
@@ -194,7 +163,7 @@ class FullbandMelganGenerator(MelganGenerator):
                          num_res_blocks=num_res_blocks)
 
 
-class ParallelWaveganGenerator(nn.Module):
+class ParallelWaveganGenerator(NativeModel):
     """``TTS/vocoder/models/parallel_wavegan_generator.py:9-158`` for the configuration
     ``setup_generator`` builds (64 res / 128 gate / 64 skip / 80 aux channels, kernel 3, bias,
     no dropout at inference): constructor, checkpoint keys (weight_g / weight_v until
@@ -203,6 +172,8 @@ class ParallelWaveganGenerator(nn.Module):
     The prior noise is ``torch.randn([B, 1, T])`` on the CPU generator, as the reference draws it
     (``:96``), so a seeded call reproduces the reference's noise; pass ``noise=`` to fix it.
     Batching (new, optional): ``lengths=`` gives per-row mel frames of a padded batch."""
+
+    _slot = "pwgan"
 
     def __init__(self, in_channels=1, out_channels=1, kernel_size=3, num_res_blocks=30, stacks=3, res_channels=64,
                  gate_channels=128, skip_channels=64, aux_channels=80, dropout=0.0, bias=True, use_weight_norm=True,
@@ -224,57 +195,26 @@ class ParallelWaveganGenerator(nn.Module):
         self.dropout = dropout
         self._wn = use_weight_norm
         populate(self, pwgan_spec(self.cfg, weight_norm=use_weight_norm))
-        self._version = 0
-        self._token = new_token()
 
     @property
     def hop(self):
         return self.upsample_scale
 
-    def load_state_dict(self, state_dict, strict=True, **kw):
-        res = super().load_state_dict(state_dict, strict=strict, **kw)
-        self._version += 1
-        return res
-
-    def _apply(self, fn, *args, **kwargs):
-        res = super()._apply(fn, *args, **kwargs)
-        self._version += 1
-        return res
-
-    def invalidate(self):
-        self._version += 1
-
     def remove_weight_norm(self):
         """Fold w = g * v / ||v|| for every weight-normed conv (parallel_wavegan_generator.py:127-135)."""
-        if not self._wn:
-            return
-        for name, shape, kind in pwgan_spec(self.cfg, weight_norm=True):
-            if not name.endswith(".weight_v"):
-                continue
-            path = name[:-len(".weight_v")].split(".")
-            m = self
-            for p in path:
-                m = m._modules[p]
-            w = torch._weight_norm(m.weight_v.data, m.weight_g.data, 0)
-            del m._parameters["weight_g"]
-            del m._parameters["weight_v"]
-            m.weight = nn.Parameter(w.contiguous(), requires_grad=False)
-        self._wn = False
-        self._version += 1
+        self._fold_weight_norm(name[:-len(".weight_v")] for name, _, _ in pwgan_spec(self.cfg, weight_norm=True)
+                               if name.endswith(".weight_v"))
 
-    def _sync(self, eng):
-        key = (self._token, self._version)
-        if eng.pwgan_key != key:
-            eng.load_pwgan(host_tensors(self), self.cfg.num_res_blocks, self.cfg.stacks, self.cfg.upsample_factors)
-            eng.pwgan_key = key
+    def _load(self, eng):
+        eng.load_pwgan(host_tensors(self), self.cfg.num_res_blocks, self.cfg.stacks, self.cfg.upsample_factors)
 
     def forward(self, c):
         raise NotImplementedError("training forward is out of scope; use inference()")
 
     @torch.no_grad()
     def inference(self, c, lengths: Optional[Sequence[int]] = None, noise: Optional[torch.Tensor] = None):
-        dev = self.first_conv.bias.device
-        eng = get_engine(dev)
+        dev = self.device
+        eng = self._engine()
         c = torch.as_tensor(c).to(dev, torch.float32)
         if c.dim() == 2:
             c = c[None]
