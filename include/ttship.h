@@ -10,6 +10,9 @@
  *   tts_taco_infer                <- Tacotron2.inference(text)  (TTS/tts/models/tacotron2.py:142-163)
  *   tts_taco_infer_spk            <- Tacotron2.inference(text, speaker_ids | speaker_embeddings)
  *                                    with decoder.set_r / max_decoder_steps (layers/tacotron2.py:209,156)
+ *   tts_taco_forward              <- Tacotron2.forward(text, text_lengths, mel_specs, mel_lengths) in eval():
+ *                                    the teacher-forced decode (models/tacotron2.py:95-140,
+ *                                    layers/tacotron2.py:300-333)
  *   tts_taco_encoder              <- embedding + Encoder.inference (models/tacotron2.py:144-145,
  *                                    layers/tacotron2.py:112-119)
  *   tts_taco_postnet              <- Postnet + residual (models/tacotron2.py:159-160)
@@ -106,6 +109,25 @@ int tts_taco_infer_spk(tts_ctx* ctx, const int64_t* d_ids, const int32_t* h_lens
                        const int32_t* h_max_steps, int S_cap, float stop_threshold, const int64_t* d_spk_ids,
                        const float* d_spk_emb, float* d_dec, float* d_post, float* d_align, float* d_stop,
                        int32_t* h_steps, int32_t* h_status, void* stream);
+
+/* Teacher-forced Tacotron2.forward(text, text_lengths, mel_specs, mel_lengths, speaker_ids,
+   speaker_embeddings) of a model in eval() (TTS/tts/models/tacotron2.py:95-140,
+   layers/tacotron2.py:300-333; notebooks/ExtractTTSpectrogram.ipynb): the decode driven by the
+   ground-truth mel. Output i equals the reference B=1 call on row i alone, on its own
+   S_i r frames, S_i = ceil(h_mel_lens[i] / r).
+   d_mel      (B, M_max, 80) float, 16-byte aligned; M_max a multiple of r. Step t >= 1 of row b reads
+              frame d_mel[b][t r - 1] (t < S_b, so never a frame at or past h_mel_lens[b])
+   h_mel_lens per-row mel lengths, 1 <= h_mel_lens[b] <= M_max; rows take exactly S_b steps (no stop rule)
+   d_spk_ids / d_spk_emb as tts_taco_infer_spk (both NULL: single-speaker model)
+   d_dec, d_post (B, M_max, 80): frames [0, h_mel_lens[b]) valid, rest zero (the output mask; the
+              postnet runs over the row's S_b r masked frames)
+   d_align    (B, M_max / r, T_max), d_stop (B, M_max / r) RAW stopnet logits; zero for steps >= S_b
+   Plain location attention only (windowing, forward and Graves attention: an error), on the
+   persistent decoder only (an error where it is not in use), at most 64 rows per call. */
+int tts_taco_forward(tts_ctx* ctx, const int64_t* d_ids, const int32_t* h_lens, int B, int T_max, int r,
+                     const float* d_mel, const int32_t* h_mel_lens, int M_max, const int64_t* d_spk_ids,
+                     const float* d_spk_emb, float* d_dec, float* d_post, float* d_align, float* d_stop,
+                     void* stream);
 
 /* Decoder options that no tensor reveals (layers/tacotron2.py:147-200 -> common_layers.py:196-372):
    attention windowing at inference (attn_win) and forward attention (forward_attn; the transition

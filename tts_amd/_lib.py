@@ -39,6 +39,8 @@ SIGNATURES = [
     ("tts_taco_infer_spk", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_int_p,
                                           ctypes.c_int, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _c_int_p,
                                           _c_int_p, _vp]),
+    ("tts_taco_forward", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _c_int_p,
+                                        ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("tts_taco_mbmelgan_infer", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                _c_int_p, ctypes.c_int, ctypes.c_float, _vp, _vp, _vp, _vp, _vp,
                                                _vp, ctypes.c_int, _vp, _c_int_p, _c_int_p, _vp]),
@@ -211,6 +213,17 @@ class Engine:
             _check(self.lib.tts_taco_infer_spk(*head, float(stop_threshold), _opt_ptr(speaker_ids),
                                                _opt_ptr(speaker_embeddings), *outs, *res, _stream(ids.device)))
         return steps, status
+
+    def taco_forward(self, ids, lens, r, mel, mel_lens, dec, post, align, stop, speaker_ids=None,
+                     speaker_embeddings=None):
+        """Teacher-forced Tacotron2.forward in eval (tts_taco_forward): ``mel`` (B, M, 80) contiguous
+        fp32 with M a multiple of r; dec / post (B, M, 80), align (B, M / r, T), stop (B, M / r)."""
+        B, T = ids.shape
+        lens_a, lens_p = _i32(lens)
+        ml_a, ml_p = _i32(mel_lens)
+        _check(self.lib.tts_taco_forward(self.h, _ptr(ids), lens_p, B, T, r, _ptr(mel), ml_p, int(mel.shape[1]),
+                                         _opt_ptr(speaker_ids), _opt_ptr(speaker_embeddings), _ptr(dec), _ptr(post),
+                                         _ptr(align), _ptr(stop), _stream(ids.device)))
 
     def taco_mbmelgan_infer(self, ids, lens, r, max_steps, S_cap, stop_threshold, dec, post, align, stop, pad, wav,
                             speaker_ids=None, speaker_embeddings=None):

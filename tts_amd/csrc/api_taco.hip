@@ -1,5 +1,6 @@
 // Tacotron2, running: the decoder step launches and their captured graphs, the encoder and
-// postnet, the persistent decoder, taco_infer, and the tts_taco_* inference entry points.
+// postnet, the persistent decoder, taco_infer, the teacher-forced taco_forward, and the tts_taco_*
+// inference entry points.
 #include "host.h"
 #include "decoder.h"
 #include "gsync.h"
@@ -419,6 +420,22 @@ __global__ void taco_mlens_kernel(const DecCtlBlock* cb, int B, int r, int* mlen
   if (i < B) mlens[i] = cb->steps[i] * r;
 }
 
+// the output mask of a teacher-forced decode: frames [M_i, steps_i r) of decode row i zeroed (at most
+// r - 1 frames: the padded part of the row's last group); one workgroup per row
+struct MelLens {
+  int M[BMAX];
+};
+__global__ void mask_frames_kernel(float* x, MelLens ml, const int* __restrict__ flens, int r, long row) {
+  const int i = blockIdx.x;
+  const int f0 = ml.M[i], f1 = min(flens[i], f0 + r);  // flens = steps * r <= S_cap r: inside the row
+  float* p = x + i * row;
+  for (int e = f0 * 80 + threadIdx.x; e < f1 * 80; e += blockDim.x) p[e] = 0.f;
+}
+void mask_frames(float* x, const MelLens& ml, const int* d_flens, int B, int r, long row, hipStream_t s) {
+  mask_frames_kernel<<<B, 256, 0, s>>>(x, ml, d_flens, r, row);
+  HIP_OK(hipGetLastError());
+}
+
 // gather every status word the host checks after a Tacotron2 call into one block (TS_* layout)
 struct DecSlots {
   int v[PMAX_LAUNCH];
@@ -656,10 +673,16 @@ void launch_cascade(tts_ctx* c, PArgs a, hipStream_t s) {
 }
 
 // the whole decode on the persistent kernel (decoder_persist.hip)
-void run_persistent(tts_ctx* c, int r, float thr, hipStream_t s) {
+// teach_steps > 0: teacher mode on W.teach (taco_forward)
+void run_persistent(tts_ctx* c, int r, float thr, hipStream_t s, int teach_steps = 0) {
   build_pj(c, r);
   grow<float>(c->tws.spkb, (size_t)64 * (8320 + 112 * 16), c->tws.gen);
-  const PArgs a = persist_args(c, r, thr);
+  PArgs a = persist_args(c, r, thr);
+  if (teach_steps > 0) {
+    a.teach = c->tws.teach.f();
+    a.teach_steps = teach_steps;
+    a.teach_rows = c->tws.MT * 16;
+  }
   stage_row_biases(c, a, s);
   reset_variant_state(c, s);
   launch_cascade(c, a, s);
@@ -811,13 +834,18 @@ void run_graph_decoder(tts_ctx* c, int B, int T_max, int S_cap, int r, float thr
 // postnet over each row's own frames: lengths from the decoder results on the device, grid sized
 // by S_cap (tiles past a row's length exit at entry), so the decode needs no host round trip; then
 // the scatter back to the caller's row order: output row b <- decode row inv[b]
+// ml (taco_forward): the rows' mel lengths M_i in decode order; the decoder outputs are zeroed at
+// frames >= M_i before the postnet, its output after it (the reference's output mask,
+// models/tacotron2.py:123-130)
 void run_postnet_scatter(tts_ctx* c, int B, int T_max, int S_cap, int r, float* d_dec, float* d_post, float* d_align,
-                         float* d_stop, hipStream_t s) {
+                         float* d_stop, hipStream_t s, const MelLens* ml = nullptr) {
   auto& W = c->tws;
   taco_mlens_kernel<<<1, 64, 0, s>>>(ctl_block(W), B, r, W.mlens.i());
   HIP_OK(hipGetLastError());
   const long fb = (long)S_cap * r * 80;  // W.post was zeroed with the decoder state
+  if (ml) mask_frames(W.dec.f(), *ml, W.mlens.i(), B, r, fb, s);
   run_postnet(c, W.dec.f(), fb, W.mlens.i(), B, S_cap * r, S_cap * r, W.post.f(), fb, s);
+  if (ml) mask_frames(W.post.f(), *ml, W.mlens.i(), B, r, fb, s);
   gather4_rows(Gather4{{W.post.f(), W.dec.f(), W.align.f(), W.stop.f()}, {d_post, d_dec, d_align, d_stop},
                        {fb, fb, (long)S_cap * T_max, (long)S_cap}},
                W.map.i() + BMAX, B, s);
@@ -909,7 +937,85 @@ void ttsh::taco_infer(tts_ctx* c, const int64_t* ids, const int32_t* h_lens, int
   c->last_r = r;
 }
 
+// Teacher-forced decode (Tacotron2.forward in eval): taco_infer's steps with the prenet fed from the
+// ground-truth mel (teacher_prenet.hip + the persistent decoder's teacher variant), exactly
+// S_i = ceil(M_i / r) steps per row, raw stop logits, and the reference's output mask
+void ttsh::taco_forward(tts_ctx* c, const int64_t* ids, const int32_t* h_lens, int B, int T_max, int r,
+                        const float* d_mel, const int32_t* h_mel_lens, int M_max, const int64_t* d_spk_ids,
+                        const float* d_spk_emb, float* d_dec, float* d_post, float* d_align, float* d_stop,
+                        void* stream) {
+  auto& M = c->taco;
+  TTS_CHECK(M.ready, "tacotron2 weights not finalized");
+  TTS_CHECK(M_max >= 1 && M_max <= (1 << 20) && r >= 1 && M_max % r == 0, "M_max must be a positive multiple of r");
+  TTS_CHECK(!M.windowing && !M.forward_attn && !M.graves,
+            "teacher-forced forward: attention windowing, forward attention and Graves attention are not implemented");
+  const int S_cap = M_max / r;
+  int32_t steps[BMAX], rsteps[BMAX], rstatus[BMAX];
+  TTS_CHECK(B >= 1 && B <= BMAX, "B must be in [1, 64]");
+  for (int b = 0; b < B; ++b) {
+    TTS_CHECK(h_mel_lens[b] >= 1 && h_mel_lens[b] <= M_max, "mel lens out of range");
+    steps[b] = (h_mel_lens[b] + r - 1) / r;
+  }
+  check_infer_args(M, h_lens, B, T_max, r, steps, S_cap);
+  taco_workspace(c, B, T_max, S_cap, r);
+  auto& W = c->tws;
+  grow<float>(W.teach, (size_t)S_cap * W.MT * 16 * 256, W.gen);
+  hipStream_t s = c->s;
+  enter(c, stream);
+  const std::vector<int> perm = stage_decode_order(c, h_lens, steps, B, nullptr, s);
+  W.thr = 0.5f;  // unused: a teacher-forced row never stops by its stop token
+  TTS_CHECK(use_persistent(c), "teacher-forced forward runs on the persistent decoder only (<= 64 utterances per "
+                               "call on a 256-CU device, TTS_DECODER=graph unset)");
+  stage_speakers(c, d_spk_ids, d_spk_emb, B, s);
+  run_encoder_penc(c, ids, B, T_max, s);
+  if (!W.pslot_cal) {
+    pick_barrier_blocks(reinterpret_cast<unsigned*>(W.pbar.p), PBAR_CAND, PMAX_LAUNCH, W.pslot, s);
+    W.pslot_cal = true;
+  }
+  fill_decoder_state(c, B, T_max, S_cap, r, true, s);
+  TeachArgs ta{};
+  ta.mel = d_mel;
+  ta.mel_b = (long)M_max * 80;
+  ta.map = W.map.i();
+  ta.max_steps = ctl_block(W)->max_steps;
+  ta.W1 = M.pre1.f();
+  ta.b1 = M.prenet_bn ? M.pre1_b0.f() : nullptr;
+  ta.teach = W.teach.f();
+  ta.B = B;
+  ta.Bp = W.MT * 16;
+  ta.r = r;
+  ta.steps = S_cap;
+  launch_teacher_prenet(ta, s);
+  c->dec_path = 1;
+  run_persistent(c, r, W.thr, s, S_cap);
+  MelLens ml{};
+  for (int i = 0; i < B; ++i) ml.M[i] = h_mel_lens[perm[i]];
+  run_postnet_scatter(c, B, T_max, S_cap, r, d_dec, d_post, d_align, d_stop, s, &ml);
+  read_status(c, B, r, true, nullptr, s);
+  report_rows(c, perm, rsteps, rstatus);
+  for (int b = 0; b < B; ++b) TTS_CHECK(rsteps[b] == steps[b], "teacher-forced decode: a row's step count (internal error)");
+  leave(c, stream);
+  c->last_B = B;
+  c->last_T = T_max;
+  c->last_S = S_cap;
+  c->last_r = r;
+}
+
 extern "C" {
+
+int tts_taco_forward(tts_ctx* c, const int64_t* d_ids, const int32_t* h_lens, int B, int T_max, int r,
+                     const float* d_mel, const int32_t* h_mel_lens, int M_max, const int64_t* d_spk_ids,
+                     const float* d_spk_emb, float* d_dec, float* d_post, float* d_align, float* d_stop,
+                     void* stream) {
+  return guarded_ctx(c, [&] {
+    TTS_CHECK(c && d_ids && h_lens && d_mel && h_mel_lens && d_dec && d_post && d_align && d_stop, "null argument");
+    DeviceGuard g(c->device);
+    with_x3_fallback(c, [&] {
+      taco_forward(c, d_ids, h_lens, B, T_max, r, d_mel, h_mel_lens, M_max, d_spk_ids, d_spk_emb, d_dec, d_post,
+                   d_align, d_stop, stream);
+    });
+  });
+}
 
 int tts_taco_infer(tts_ctx* c, const int64_t* d_ids, const int32_t* h_lens, int B, int T_max, int r,
                    const int32_t* h_max_steps, int S_cap, float thr, float* d_dec, float* d_post, float* d_align,

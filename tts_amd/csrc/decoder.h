@@ -196,7 +196,26 @@ struct PArgs {
   int trace_t0;
   unsigned* diag;  // optional (TTS_DIAG_XCC): the XCC id of every workgroup, written at launch
   DecDev D;
+  // teacher mode (Tacotron2.forward; selects the kernel's V_TEACH variant): prenet layer 1 of the
+  // ground-truth frames, [teach_steps][teach_rows][256] row-major (teacher_prenet.hip); step t >= 1
+  // reads teach[t - 1] where the free-running decode reads the folded projection, the stop block
+  // stores raw logits and rows end at max_steps only
+  const float* teach;
+  int teach_steps, teach_rows;
 };
+
+// prenet layer 1 of every teacher frame (teacher_prenet.hip): teach[t - 1][m] for steps t = 1 .. steps
+struct TeachArgs {
+  const float* mel;      // (B, M_max, 80) ground-truth frames, caller row order, 16-byte aligned
+  long mel_b;            // floats between rows (M_max * 80)
+  const int* map;        // decode row -> caller row
+  const int* max_steps;  // decode order: row m takes steps t < max_steps[m]
+  const float* W1;       // swizzled [16][5][64][4] (BN folded)
+  const float* b1;       // [256] BN-folded bias b1', or null
+  float* teach;          // [steps][Bp][256]
+  int B, Bp, r, steps;
+};
+void launch_teacher_prenet(const TeachArgs& a, hipStream_t s);
 
 bool persist_supported(int device);
 int persist_attn_tc();  // attention positions per work item (sizes the chunk-partial buffers)

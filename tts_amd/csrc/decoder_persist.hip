@@ -58,8 +58,12 @@ constexpr int YROWS = 64;    // rows per projection half (independent of the bat
 // the decoder variants compiled into persist_decoder_kernel<MT, VAR>, as bits of VAR: attention
 // windowing, forward attention, Graves attention (which replaces the location-sensitive attention,
 // so it excludes the other two), P3's attention_rnn prenet part on the split-f16 MFMA (attp_x3 given)
-constexpr int V_WIN = 1, V_FWD = 2, V_GRAVES = 4, V_X3 = 8, V_N = 16;
-constexpr bool var_valid(int VAR) { return !(VAR & V_GRAVES) || !(VAR & (V_WIN | V_FWD)); }
+// V_TEACH: teacher mode (Tacotron2.forward): P1 reads prenet layer 1 of the ground-truth frame from
+// P.teach, the stop block stores raw logits and never stops a row; plain location attention only
+constexpr int V_WIN = 1, V_FWD = 2, V_GRAVES = 4, V_X3 = 8, V_TEACH = 16, V_N = 32;
+constexpr bool var_valid(int VAR) {
+  return (!(VAR & V_GRAVES) || !(VAR & (V_WIN | V_FWD))) && (!(VAR & V_TEACH) || !(VAR & (V_WIN | V_FWD | V_GRAVES)));
+}
 // encoder rows (of 8 per thread) an attention item keeps in registers across steps: 4 where the
 // kernel stays within 256 VGPRs without spills (split-f16 variants without forward attention), 0
 // elsewhere (and for 48 / 64-row batch tiles, whose accumulators need the registers); pec_arr
@@ -71,7 +75,7 @@ constexpr int pec_arr(int VAR, int MT) { return pec_of(VAR, MT) > 0 ? pec_of(VAR
 // fragment quad takes in fp32, so the streaming consumers feed the loads to the MFMA without
 // splitting (the split is done once, by the producer; tools/payload_bench.hip mode 3: 0.42 us less
 // per streamed 192 KB block). The variants with fp32 readers of these buffers keep fp32.
-constexpr bool presplit_of(int VAR) { return VAR == V_X3; }
+constexpr bool presplit_of(int VAR) { return (VAR & ~V_TEACH) == V_X3; }
 template <bool PS>
 __device__ __forceinline__ void stc_quad_h(float* base, int e, float v) {
   if constexpr (PS) stc_quad_x3(base, e, v);
@@ -969,6 +973,7 @@ __global__ __launch_bounds__(PT) void persist_decoder_kernel(PArgs P) {
   constexpr bool X3P = (VAR & V_X3) != 0;     // P3's attention_rnn prenet part on the split-f16 MFMA
   constexpr bool DEFER = (VAR & (V_WIN | V_FWD | V_GRAVES)) == 0;  // plain location attention: alignment pass deferred to P6
   constexpr bool PS = presplit_of(VAR);    // h_att, ctx, h_dec published pre-split
+  constexpr bool TEACH = (VAR & V_TEACH) != 0;  // teacher-forced decode (P.teach)
   extern __shared__ __attribute__((aligned(16))) f32x4 smem4[];
   __shared__ int sflag, is_last;
   constexpr int Bp = MT * 16;
@@ -1151,7 +1156,10 @@ __global__ __launch_bounds__(PT) void persist_decoder_kernel(PArgs P) {
         for (int h = 0; h < 2; ++h) {
           const int kc = 8 * h + wave;
           const int col = P.nt_proj * 16 + kc * 16 + 4 * (lane >> 4);
-          if (t > 0) {
+          if (TEACH && t > 0) {  // layer 1 of the ground-truth frame mel[t r - 1] (teacher_prenet.hip)
+            x[h] = *reinterpret_cast<const f32x4*>(P.teach + ((long)min(t - 1, P.teach_steps - 1) * P.teach_rows + m) * 256 +
+                                                   kc * 16 + 4 * (lane >> 4));
+          } else if (t > 0) {
             const f32x4 bb = pjb4(m, col);
             x[h] = X3P ? ldc4(P.ypart, (m * YP + col) * 4) + bb
                        : ldc4(P.ypart, (m * YP + col) * 4) + ldc4(P.ypart, ((YROWS + m) * YP + col) * 4) + bb;
@@ -1200,9 +1208,9 @@ __global__ __launch_bounds__(PT) void persist_decoder_kernel(PArgs P) {
         const int msteps = D.max_steps[m];
         if (t >= 1 && !dn) {
           const float logit = y0 + y1 + yb;
-          const float sg = sigm(logit);
+          const float sg = TEACH ? logit : sigm(logit);  // forward returns the raw stopnet logits
           if (t - 1 < D.S_cap) D.stop_out[(long)m * D.S_cap + (t - 1)] = sg;
-          const bool st = (sg > P.thr) && (t - 1) > 0;
+          const bool st = !TEACH && (sg > P.thr) && (t - 1) > 0;  // teacher mode: rows end at max_steps
           if (st || t >= msteps) {
             stci(D.done + m, 1);
             stci(D.steps + m, t);
@@ -1763,7 +1771,8 @@ std::array<const void*, V_N> pdk_row(std::integer_sequence<int, V...>) {
 }
 
 static int persist_var(const PArgs& a) {
-  return (a.gK > 0 ? V_GRAVES : (a.win ? V_WIN : 0) | (a.fwd ? V_FWD : 0)) | (a.attp_x3 ? V_X3 : 0);
+  return (a.gK > 0 ? V_GRAVES : (a.win ? V_WIN : 0) | (a.fwd ? V_FWD : 0)) | (a.attp_x3 ? V_X3 : 0) |
+         (a.teach ? V_TEACH : 0);
 }
 bool persist_presplit(const PArgs& a) { return presplit_of(persist_var(a)); }
 
@@ -1776,6 +1785,8 @@ void launch_persist_decoder(const PArgs& a, int MT, hipStream_t s, bool arm, hip
   TTS_CHECK(!a.attp_x3 || (a.x3flag && a.dec_x3 && a.apre_x3 && a.pj_x3),
             "persistent decoder: split-f16 weights incomplete or without a range flag");
   const int var = persist_var(a);
+  TTS_CHECK(!a.teach || (var_valid(var) && a.teach_steps >= 1 && a.teach_rows >= 16 * MT),
+            "persistent decoder: teacher mode takes plain location attention and a teacher buffer of the launch's rows");
   // the variants are compiled in only where valid (var_valid); the other entries stay null
   constexpr std::make_integer_sequence<int, V_N> vs{};
   static const std::array<const void*, V_N> fns[4] = {pdk_row<1>(vs), pdk_row<2>(vs), pdk_row<3>(vs), pdk_row<4>(vs)};

@@ -206,6 +206,7 @@ struct TacoWS {
   DevBuf spk, spkid, spkb;     // speaker vectors (decode order), per-row biases [Bp][NSPK]
   DevBuf win_idx, fwd_u, apf;  // windowing argmax, transition probability, forward chunk sums
   DevBuf gh, gmu;              // Graves: N_a hidden (32 x 1024), mixture means (64 x 16)
+  DevBuf teach;                // teacher-forced decode: prenet layer 1 of the ground-truth frames [S_cap][Bp][256]
   DevBuf trace, xdiag;         // TTS_PTRACE / TTS_DIAG_XCC diagnostics, on this context's device
   bool enc_persist = false;    // the last encoder ran the persistent BiLSTM (lc = its barrier words)
   int enc_ndom = 0;            // its recurrences (directions x row groups), one barrier block each
@@ -566,6 +567,11 @@ void taco_infer(tts_ctx* c, const int64_t* ids, const int32_t* h_lens, int B, in
                 const int32_t* h_max_steps, int S_cap, float thr, float* d_dec, float* d_post, float* d_align,
                 float* d_stop, int32_t* h_steps, int32_t* h_status, void* stream,
                 const int64_t* d_spk_ids = nullptr, const float* d_spk_emb = nullptr, const FusedVoc* fv = nullptr);
+
+// Tacotron2.forward in eval (tts_taco_forward): d_mel (B, M_max, 80), M_max a multiple of r
+void taco_forward(tts_ctx* c, const int64_t* ids, const int32_t* h_lens, int B, int T_max, int r, const float* d_mel,
+                  const int32_t* h_mel_lens, int M_max, const int64_t* d_spk_ids, const float* d_spk_emb, float* d_dec,
+                  float* d_post, float* d_align, float* d_stop, void* stream);
 
 // --- MelGAN: api_melgan.hip, for the fused path
 // returns total upsampling factor; writes bands (B, out_ch, up*(M_max+2pad)) into `out`

@@ -16,9 +16,10 @@ run B > 1: ``layers/tacotron2.py:362``). Per-utterance lengths are in ``last_ste
 
 from typing import Optional, Sequence
 
+import numpy as np
 import torch
 
-from .params import Container, host_tensors, populate
+from .params import Container, host_tensors, populate, row_lengths
 from .spec import TacotronConfig, tacotron2_spec
 from .tacotron_host import TacotronHost
 
@@ -178,6 +179,89 @@ class Tacotron2(TacotronHost):
                 outs.append((dec, post, align, stop, steps, status))
         self._last_call = (B, int(lens.max()), len(outs))
         return self._assemble(outs, text.shape, r, dev)
+
+    @torch.no_grad()
+    def forward(self, text, text_lengths, mel_specs=None, mel_lengths=None, speaker_ids=None,
+                speaker_embeddings=None):
+        """The reference's ``forward`` on a model in ``eval()`` (models/tacotron2.py:95-140,
+        layers/tacotron2.py:300-333): the decode driven by the ground-truth ``mel_specs`` (B, M, 80),
+        as notebooks/ExtractTTSpectrogram.ipynb calls it for ground-truth-aligned mels and forced
+        alignments. Returns (decoder_outputs (B, M, 80), postnet_outputs (B, M, 80), alignments
+        (B, M / r, T), stop_tokens (B, M / r), raw stopnet logits).
+
+        Row i equals the reference B = 1 call on that row alone, ``forward(text[i:i+1, :T_i], [T_i],
+        mel_specs[i:i+1, :S_i * r], [M_i])`` with ``S_i = ceil(M_i / r)``: it takes S_i steps, and
+        everything past its own extent (frames >= M_i, steps >= S_i, positions >= T_i) is zero.
+        ``mel_lengths=None``: every row has M frames. ``text_lengths`` need not be sorted. Models
+        with ``double_decoder_consistency`` / ``bidirectional_decoder`` return the same 4-tuple (the
+        reference adds two training-loss tensors). ``last_steps`` holds S_i, ``last_mel_lengths`` M_i.
+        Training (``self.training``) stays out of scope."""
+        if self.training:
+            return super().forward()
+        for on, name in ((self.cfg.attn_type == "graves", 'attn_type="graves"'), (self.cfg.windowing, "attn_win"),
+                         (self.cfg.forward_attn, "forward_attn")):
+            if on:
+                raise NotImplementedError(f"tts_amd Tacotron2.forward does not implement {name} (inference() does)")
+        if mel_specs is None:
+            raise ValueError("forward is teacher-forced: mel_specs (B, M, 80) is required")
+        text = torch.as_tensor(text)
+        if text.dim() == 1:
+            text = text[None]
+        mel = torch.as_tensor(mel_specs)
+        if mel.dim() != 3 or mel.shape[2] != self.decoder.frame_channels:
+            raise ValueError(f"mel_specs must be (B, M, {self.decoder.frame_channels})")
+        B, T = text.shape
+        if mel.shape[0] != B:
+            raise ValueError("mel_specs must have one row per row of text")
+        lens = row_lengths(text_lengths, B, T, "text_lengths")
+        r = int(self.decoder.r)
+        if not 1 <= r <= self.decoder.r_init:
+            raise ValueError(f"r={r} must be in [1, r_init={self.decoder.r_init}]")
+        M = int(mel.shape[1])
+        if M < 1 or M % r != 0:  # the reference's memory.view(B, M // r, -1) (layers/tacotron2.py:241)
+            raise RuntimeError(f"shape '[{B}, {M // r}, -1]' is invalid for input of size {mel.numel()}: "
+                               f"mel_specs.shape[1] must be a multiple of r={r}")
+        mlens = np.full(B, M, np.int64) if mel_lengths is None else \
+            np.asarray(torch.as_tensor(mel_lengths).cpu(), dtype=np.int64).reshape(-1)
+        if len(mlens) != B or mlens.min() < 1 or mlens.max() > M:
+            raise ValueError("mel_lengths must have B entries in [1, M]")
+        dev = self.device
+        spk_ids, spk_emb = self._speaker_args(speaker_ids, speaker_embeddings, B, dev)
+        eng = self._engine()  # a CPU model stops here: there is no CPU fallback
+        text = text.to(dev, torch.int64).contiguous()
+        mel = mel.to(dev, torch.float32)
+        steps = -(-mlens // r)
+        S = M // r
+        outs = []
+        with eng.lock:
+            self._sync(eng)
+            for b0 in range(0, B, SPEAKER_BATCH_LIMIT):
+                b1 = min(B, b0 + SPEAKER_BATCH_LIMIT)
+                Tn, Sn = int(lens[b0:b1].max()), int(steps[b0:b1].max())
+                dec, post, align, stop = self._out_tensors(b1 - b0, Sn, r, Tn, dev)
+                eng.taco_forward(text[b0:b1, :Tn].contiguous(), lens[b0:b1], r, mel[b0:b1, :Sn * r].contiguous(),
+                                 mlens[b0:b1], dec, post, align, stop,
+                                 speaker_ids=None if spk_ids is None else spk_ids[b0:b1].contiguous(),
+                                 speaker_embeddings=None if spk_emb is None else spk_emb[b0:b1].contiguous())
+                outs.append((dec, post, align, stop))
+        if len(outs) == 1 and outs[0][2].shape[1:] == (S, T):
+            dec, post, align, stop = outs[0]
+        else:  # library calls cover their own longest row: zero-extended to the call's (M, S, T)
+            dec = torch.zeros(B, M, 80, device=dev)
+            post = torch.zeros(B, M, self.postnet_output_dim, device=dev)
+            align = torch.zeros(B, S, T, device=dev)
+            stop = torch.zeros(B, S, device=dev)
+            b0 = 0
+            for d_, p_, a_, s_ in outs:
+                n, Sn, Tn = a_.shape
+                dec[b0:b0 + n, :Sn * r], post[b0:b0 + n, :Sn * r] = d_, p_
+                align[b0:b0 + n, :Sn, :Tn], stop[b0:b0 + n, :Sn] = a_, s_
+                b0 += n
+        self._last_call = (B, int(lens.max()), len(outs))
+        self.last_steps = steps.astype(np.int32)
+        self.last_mel_lengths = mlens.astype(np.int32)
+        self.last_status = None
+        return dec, post, align, stop
 
     @torch.no_grad()
     def inference_vocoded(self, text, vocoder, speaker_ids=None, speaker_embeddings=None,
