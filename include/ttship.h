@@ -253,6 +253,23 @@ int tts_glow_encode_spk(tts_ctx* ctx, const int64_t* d_ids, const int32_t* h_len
                         int B, int T_max, float length_scale, int32_t* h_ylens, void* stream);
 int tts_glow_decode(tts_ctx* ctx, const float* d_noise, float noise_scale, int Ty, float* d_y, float* d_ymean,
                     float* d_attn, float* d_logw, void* stream);
+/* tts_glow_align <- GlowTts.forward in eval (glow_tts.py:114-156), the analysis direction, for the
+   batch of the preceding tts_glow_encode / _encode_spk (it reuses that call's o_mean, o_dur_log,
+   lengths and speaker conditioning). d_y (B, 80, Ty) is the mel, h_ylens its frames per row; each is
+   rounded down to even and Te = 2 * floor(Ty / 2) (preprocess, :187-194). Out: d_z (B, 80, Te) the
+   latent of the forward flows, d_logdet (B) their log-determinant, d_logp (B, T_max, Te) the
+   likelihood matrix (:141-150; zero outside a row's lengths; NULL: kept internal), d_attn
+   (B, Te, T_max) the monotonic alignment, d_ymean (B, 80, Te) the encoder means along it,
+   d_oattn_dur (B, T_max) = log(1 + frames per token), d_logw (B, T_max) = o_dur_log. The alignment
+   search runs on the device (no host round trip) and repeats maximum_path_c's arithmetic, so the
+   path is a function of logp's bits. Fails if a row has fewer even-rounded frames than tokens, or
+   fewer than 2: the reference's search reads outside its band there. */
+int tts_glow_align(tts_ctx* ctx, const float* d_y, const int32_t* h_ylens, int Ty, float* d_z, float* d_logdet,
+                   float* d_logp, float* d_attn, float* d_ymean, float* d_oattn_dur, float* d_logw, void* stream);
+/* tts_glow_mas <- maximum_path (layers/glow_tts/monotonic_align) alone: d_logp (B, Tx, Ty), per-row
+   h_xlens <= h_ylens; d_path (B, Tx, Ty) holds 1 on the path and 0 elsewhere. B <= 64, Tx <= 4096. */
+int tts_glow_mas(tts_ctx* ctx, const float* d_logp, const int32_t* h_xlens, const int32_t* h_ylens, int B, int Tx,
+                 int Ty, float* d_path, void* stream);
 
 /* ---- GE2E speaker encoder (TTS/speaker_encoder/model.py) ----
    tts_ge2e_set_tensor/finalize <- SpeakerEncoder(input_dim, proj_dim, lstm_dim, num_lstm_layers,

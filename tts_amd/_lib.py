@@ -85,6 +85,8 @@ SIGNATURES = [
     ("tts_glow_encode_spk", ctypes.c_int, [_vp, _vp, _c_int_p, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_float,
                                            _c_int_p, _vp]),
     ("tts_glow_decode", ctypes.c_int, [_vp, _vp, ctypes.c_float, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
+    ("tts_glow_align", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("tts_glow_mas", ctypes.c_int, [_vp, _vp, _c_int_p, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp]),
     ("tts_time_decoder_kernel", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _c_f_p]),
     ("tts_decoder_stats", ctypes.c_int, [_vp, _c_i_p, _c_i_p, _c_f_p, _c_i_p]),
     ("tts_set_gemm_mode", ctypes.c_int, [_vp, ctypes.c_int]),
@@ -342,6 +344,23 @@ class Engine:
     def glow_decode(self, noise, noise_scale, Ty, y, y_mean, attn, logw):
         _check(self.lib.tts_glow_decode(self.h, _ptr(noise), float(noise_scale), Ty, _ptr(y), _ptr(y_mean),
                                         _ptr(attn), _ptr(logw), _stream(y.device)))
+
+    def glow_align(self, y, ylens, z, logdet, logp, attn, y_mean, o_attn_dur, logw):
+        """GlowTts.forward after glow_encode of the same batch; ``logp`` may be None."""
+        yl_a, yl_p = _i32(ylens)
+        _check(self.lib.tts_glow_align(self.h, _ptr(y), yl_p, int(y.shape[2]), _ptr(z), _ptr(logdet),
+                                       _opt_ptr(logp), _ptr(attn), _ptr(y_mean),
+                                       _ptr(o_attn_dur), _ptr(logw), _stream(y.device)))
+
+    def glow_mas(self, logp, xlens, ylens):
+        """maximum_path on the device: logp (B, Tx, Ty) float32 -> path (B, Tx, Ty) of 0 / 1."""
+        B, Tx, Ty = logp.shape
+        import torch
+        xl_a, xl_p = _i32(xlens)
+        yl_a, yl_p = _i32(ylens)
+        path = torch.empty_like(logp)
+        _check(self.lib.tts_glow_mas(self.h, _ptr(logp), xl_p, yl_p, B, Tx, Ty, _ptr(path), _stream(logp.device)))
+        return path
 
     def load_ge2e(self, tensors: Dict[str, np.ndarray], input_dim, proj_dim, lstm_dim, num_layers, with_proj):
         self._load_model("ge2e", tensors, input_dim, proj_dim, lstm_dim, num_layers, 1 if with_proj else 0)

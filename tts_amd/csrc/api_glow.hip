@@ -187,6 +187,9 @@ void glow_finalize(tts_ctx* c, int num_chars, int enc_layers, int flows, int wn_
   G.end.resize(flows);
   G.invtab.clear();
   G.invtab.resize(flows);
+  G.fwdtab.clear();
+  G.fwdtab.resize(flows);
+  G.fwd_logdet_frame = 0.0;
   G.wn_in.clear();
   G.wn_in.resize(flows * wn_layers);
   G.wn_rs.clear();
@@ -235,6 +238,7 @@ void glow_finalize(tts_ctx* c, int num_chars, int enc_layers, int flows, int wn_
     double a[4][8];
     for (int r = 0; r < 4; ++r)
       for (int q = 0; q < 8; ++q) a[r][q] = q < 4 ? w4[r * 4 + q] : (q - 4 == r ? 1.0 : 0.0);
+    double det = 1.0;  // product of the pivots, sign flipped per row swap
     for (int col = 0; col < 4; ++col) {  // Gauss-Jordan with partial pivoting
       int piv = col;
       for (int r = col + 1; r < 4; ++r)
@@ -242,6 +246,7 @@ void glow_finalize(tts_ctx* c, int num_chars, int enc_layers, int flows, int wn_
       for (int q = 0; q < 8; ++q) std::swap(a[col][q], a[piv][q]);
       TTS_CHECK(std::fabs(a[col][col]) > 1e-12, "glow: singular InvConvNear weight");
       const double d = a[col][col];
+      det *= piv == col ? d : -d;
       for (int q = 0; q < 8; ++q) a[col][q] /= d;
       for (int r = 0; r < 4; ++r)
         if (r != col) {
@@ -260,6 +265,19 @@ void glow_finalize(tts_ctx* c, int num_chars, int enc_layers, int flows, int wn_
       tab[cp2 * 6 + 5] = std::exp(-logs[cp2]);
     }
     G.invtab[k].upload(tab);
+    // forward of [ActNorm, InvConvNear] (glow.py:82, 192-203): the weight itself; logdet(W) is NaN
+    // for det <= 0, as torch.logdet gives it (glow.py:196)
+    std::vector<float> ftab((size_t)C2 * 6);
+    double logs_sum = 0.0;
+    for (int cp2 = 0; cp2 < C2; ++cp2) {
+      const int s2 = 2 * (cp2 / C) + cp2 % 2;
+      for (int s1 = 0; s1 < 4; ++s1) ftab[cp2 * 6 + s1] = w4[s2 * 4 + s1];
+      ftab[cp2 * 6 + 4] = abias[cp2];
+      ftab[cp2 * 6 + 5] = (float)std::exp((double)logs[cp2]);
+      logs_sum += (double)logs[cp2];
+    }
+    G.fwdtab[k].upload(ftab);
+    G.fwd_logdet_frame += logs_sum + std::log(det) * (C2 / 4);
   }
   if (cin > 0) pack_conv(G.cond, cond_w, cond_b, cpad, flows * wn_layers * 2 * H, 1, 1, 1, p0);
   HIP_OK(hipDeviceSynchronize());
@@ -304,6 +322,7 @@ void glow_encode(tts_ctx* c, const int64_t* d_ids, const int32_t* h_lens, const 
   W.Tx = T;
   W.has_g = h_spk != nullptr;
   std::vector<int> lens(h_lens, h_lens + B);
+  W.h_xlens = lens;  // glow_align checks its mel lengths against them
   HIP_OK(hipMemcpyAsync(W.lens.p, lens.data(), B * 4, hipMemcpyHostToDevice, s));
   const int* dl = W.lens.i();
   if (W.has_g) {
@@ -427,6 +446,56 @@ void glow_encode(tts_ctx* c, const int64_t* d_ids, const int32_t* h_lens, const 
   W.Ty = mx;
 }
 
+// One coupling block's network on the squeezed (B, rows, K) activations, shared by both directions
+// (glow.py:249-251 up to `end`): start(x0) -> WN (glow.py:118-138) into the skip rows of W.whs, which
+// the block's end conv reads next. Every buffer has its own batch stride (in rows).
+struct FlowConvs {
+  tts_ctx* c;
+  const int* kl;  // squeezed lengths (device)
+  int B, K;
+  void conv(const ConvLayer& L, const float* in, int in_rows, float* out, int out_rows, const float* resid, int epi,
+            int resid_rows = 0, const float* aux = nullptr) const {
+    const auto& G = c->glow;
+    ConvCall cc;
+    cc.lens = kl;
+    cc.B = B;
+    cc.oflow = x3_flag(c);
+    cc.max_q = K;
+    cc.s[0] = src_of(in, (long)in_rows * K, K, 1, L.Cin, 0);
+    cc.out = out;
+    cc.ob = (long)out_rows * K;
+    cc.oc = K;
+    cc.ot = 1;
+    cc.resid = resid;
+    cc.rb = (long)out_rows * K;
+    cc.rc = K;
+    cc.rt = 1;
+    cc.epi = epi;
+    cc.resid_rows = resid_rows;
+    cc.aux = aux;
+    cc.auxb = (long)G.flows * G.wn_layers * 2 * G.H;  // epi 3: gcond's batch stride
+    run_conv(L, cc, c->s);
+  }
+  // returns the skip rows (B, H of 2H, K)
+  float* wn(int k, const float* x) const {
+    const auto& G = c->glow;
+    auto& W = c->glws;
+    const int H = G.H;
+    float* hid = W.whs.f();  // [hidden | skip] (B, 2H, K)
+    float* skip = W.whs.f() + (size_t)H * K;
+    conv(G.start[k], x, 2 * G.C, hid, 2 * H, nullptr, 0);
+    for (int i = 0; i < G.wn_layers; ++i) {
+      const int li = k * G.wn_layers + i;
+      // gate fused; with g, cond_layer(g)'s slice for this layer is a per-utterance gate bias
+      conv(G.wn_in[li], hid, 2 * H, W.wacts.f(), H, nullptr, 3, 0, W.has_g ? W.gcond.f() + (size_t)li * 2 * H : nullptr);
+      // skip rows start at the first layer's output (no accumulate), hidden rows add the residual
+      if (i < G.wn_layers - 1) conv(G.wn_rs[li], W.wacts.f(), H, hid, 2 * H, hid, 0, i == 0 ? H : 0);
+      else conv(G.wn_rs[li], W.wacts.f(), H, skip, 2 * H, i == 0 ? nullptr : skip, 0);
+    }
+    return skip;
+  }
+};
+
 // expand + noise + reverse flows after glow_encode: d_y (B, 80, 2*(Ty/2)), d_ymean (B, 80, Ty),
 // d_attn (B, Ty, Tx), d_logw (B, Tx) = o_dur_log; d_noise (B, 80, Ty) standard normal or null
 void glow_decode(tts_ctx* c, const float* d_noise, float noise_scale, int Ty, float* d_y, float* d_ymean,
@@ -454,50 +523,124 @@ void glow_decode(tts_ctx* c, const float* d_noise, float noise_scale, int Ty, fl
   HIP_OK(hipMemcpyAsync(W.klens.p, W.h_klens.data(), B * 4, hipMemcpyHostToDevice, s));
   const int* kl = W.klens.i();
   launch_glow_squeeze(W.z.f(), C, Ty, W.ylens.i(), W.sq.f(), K, B, s);
-  // every activation is (B, rows, K) with a per-buffer batch stride (in rows)
-  auto conv = [&](const ConvLayer& L, const float* in, int in_rows, float* out, int out_rows, const float* resid,
-                  int epi, int resid_rows = 0, const float* aux = nullptr) {
-    ConvCall cc;
-    cc.lens = kl;
-    cc.B = B;
-    cc.oflow = x3_flag(c);
-    cc.max_q = K;
-    cc.s[0] = src_of(in, (long)in_rows * K, K, 1, L.Cin, 0);
-    cc.out = out;
-    cc.ob = (long)out_rows * K;
-    cc.oc = K;
-    cc.ot = 1;
-    cc.resid = resid;
-    cc.rb = (long)out_rows * K;
-    cc.rc = K;
-    cc.rt = 1;
-    cc.epi = epi;
-    cc.resid_rows = resid_rows;
-    cc.aux = aux;
-    cc.auxb = (long)G.flows * G.wn_layers * 2 * H;  // epi 3: gcond's batch stride
-    run_conv(L, cc, s);
-  };
+  const FlowConvs fc{c, kl, B, K};
   float* x = W.sq.f();
   float* x2 = W.sq2.f();
-  float* hid = W.whs.f();                 // [hidden | skip] (B, 2H, K)
-  float* skip = W.whs.f() + (size_t)H * K;
   for (int k = G.flows - 1; k >= 0; --k) {
     // CouplingBlock reverse (glow.py:245-262): WN over start(x0), then z1 = (x1 - m) exp(-logs)
-    conv(G.start[k], x, C2, hid, 2 * H, nullptr, 0);
-    for (int i = 0; i < G.wn_layers; ++i) {  // WN (glow.py:118-138)
-      const int li = k * G.wn_layers + i;
-      // gate fused; with g, cond_layer(g)'s slice for this layer is a per-utterance gate bias
-      conv(G.wn_in[li], hid, 2 * H, W.wacts.f(), H, nullptr, 3, 0, W.has_g ? W.gcond.f() + (size_t)li * 2 * H : nullptr);
-      // skip rows start at the first layer's output (no accumulate), hidden rows add the residual
-      if (i < G.wn_layers - 1) conv(G.wn_rs[li], W.wacts.f(), H, hid, 2 * H, hid, 0, i == 0 ? H : 0);
-      else conv(G.wn_rs[li], W.wacts.f(), H, skip, 2 * H, i == 0 ? nullptr : skip, 0);
-    }
+    const float* skip = fc.wn(k, x);
     // end conv + coupling + inverse InvConvNear / ActNorm: reads x, writes the next x
-    conv(G.end[k], skip, 2 * H, x2, C2, x, 5, 0, G.invtab[k].f());
+    fc.conv(G.end[k], skip, 2 * H, x2, C2, x, 5, 0, G.invtab[k].f());
     std::swap(x, x2);
   }
   launch_glow_unsqueeze(x, C2, K, W.ylens.i(), d_y, 2 * K, B, s);
   HIP_OK(hipStreamSynchronize(s));
+}
+
+// the alignment search and what follows it, on W.logp-shaped values: logp (B, Tx, Ty) with the rows'
+// lengths on the device (xl, yl) -> W.xof (B, Ty)
+void glow_search(tts_ctx* c, const float* d_logp, const int* xl, const int* yl, int max_xlen, int B, int Tx, int Ty) {
+  auto& W = c->glws;
+  long gen = 0;
+  grow<unsigned long long>(W.masbits, (size_t)B * glow_mas_bits_words(Tx, Ty), gen);
+  grow<int>(W.xof, (size_t)B * Ty, gen);
+  launch_glow_mas(d_logp, Tx, Ty, xl, yl, max_xlen, static_cast<unsigned long long*>(W.masbits.p), W.xof.i(), B, c->s);
+}
+
+// GlowTts.forward after glow_encode of the same batch (glow_tts.py:131-156): forward flows over the
+// mel d_y (B, 80, Ty) -> d_z (B, 80, Te), d_logdet (B); logp (B, Tx, Te) (d_logp or the workspace);
+// the monotonic path -> d_attn (B, Te, Tx), d_ymean (B, 80, Te), d_oattn_dur (B, Tx); d_logw (B, Tx).
+// Te = 2 floor(Ty / 2), each y_len rounded down to even (preprocess, :187-194).
+void glow_align(tts_ctx* c, const float* d_y, const int32_t* h_ylens, int Ty, float* d_z, float* d_logdet,
+                float* d_logp, float* d_attn, float* d_ymean, float* d_oattn_dur, float* d_logw) {
+  auto& G = c->glow;
+  auto& W = c->glws;
+  TTS_CHECK(G.ready, "glow weights not finalized");
+  TTS_CHECK(W.B > 0, "glow: align after encode of the same batch");
+  const int B = W.B, Tx = W.Tx, H = G.H, C = G.C, C2 = 2 * C, K = Ty / 2, Te = 2 * K;
+  TTS_CHECK(Ty >= 2, "glow align: the mel needs at least 2 frames");
+  W.h_aylens.resize(B);
+  W.h_aklens.resize(B);
+  TTS_CHECK((int)W.h_xlens.size() == B, "glow: align after encode of the same batch");
+  int max_xlen = 1;
+  for (int b = 0; b < B; ++b) {
+    TTS_CHECK(h_ylens[b] >= 0 && h_ylens[b] <= Ty, "glow align: y_lengths out of range");
+    const int ye = h_ylens[b] / 2 * 2, xl = W.h_xlens[b];
+    // below that the reference's search reads outside its band (core.pyx:18-35)
+    TTS_CHECK(ye >= 2 && ye >= xl, "glow align: row " + std::to_string(b) + " has " + std::to_string(ye) +
+                                       " mel frames (rounded down to even) for " + std::to_string(xl) +
+                                       " tokens; the alignment needs at least max(2, tokens)");
+    W.h_aylens[b] = ye;
+    W.h_aklens[b] = ye / 2;
+    max_xlen = std::max(max_xlen, xl);
+  }
+  hipStream_t s = c->s;
+  const int tiles = (K + 63) / 64;
+  long gen = 0;
+  grow<int>(W.aylens, 64, gen);
+  grow<int>(W.aklens, 64, gen);
+  grow<float>(W.sq, (size_t)B * C2 * K, gen);
+  grow<float>(W.sq2, (size_t)B * C2 * K, gen);
+  grow<float>(W.eo, (size_t)B * C2 * K, gen);
+  grow<float>(W.whs, (size_t)B * 2 * H * K, gen);
+  grow<float>(W.wacts, (size_t)B * H * K, gen);
+  grow<double>(W.ldpart, (size_t)G.flows * B * tiles, gen);
+  if (!d_logp) {
+    grow<float>(W.logp, (size_t)B * Tx * Te, gen);
+    d_logp = W.logp.f();
+  }
+  HIP_OK(hipMemcpyAsync(W.aylens.p, W.h_aylens.data(), B * 4, hipMemcpyHostToDevice, s));
+  HIP_OK(hipMemcpyAsync(W.aklens.p, W.h_aklens.data(), B * 4, hipMemcpyHostToDevice, s));
+  const int* yl = W.aylens.i();
+  const int* kl = W.aklens.i();
+  launch_glow_squeeze(d_y, C, Ty, yl, W.sq.f(), K, B, s);
+  const FlowConvs fc{c, kl, B, K};
+  float* x = W.sq.f();
+  float* x2 = W.sq2.f();
+  // ActNorm + InvConvNear of block 0 on the squeezed mel
+  launch_glow_fwd_glue(x, nullptr, G.fwdtab[0].f(), x2, C, K, kl, nullptr, B, s);
+  std::swap(x, x2);
+  for (int k = 0; k < G.flows; ++k) {
+    // CouplingBlock forward (glow.py:247-266): the reverse direction's network, a plain end conv
+    // ((m_c, logs_c) row pairs), then the coupling with ActNorm + InvConvNear of block k + 1
+    const float* skip = fc.wn(k, x);
+    fc.conv(G.end[k], skip, 2 * H, W.eo.f(), C2, nullptr, 0);
+    launch_glow_fwd_glue(x, W.eo.f(), k + 1 < G.flows ? G.fwdtab[k + 1].f() : nullptr, x2, C, K, kl,
+                         static_cast<double*>(W.ldpart.p) + (size_t)k * B * tiles, B, s);
+    std::swap(x, x2);
+  }
+  launch_glow_unsqueeze(x, C2, K, yl, d_z, Te, B, s);
+  launch_glow_logdet(static_cast<const double*>(W.ldpart.p), G.flows, tiles, B, kl, G.fwd_logdet_frame, d_logdet, s);
+  launch_glow_logp(W.om.f(), C, Tx, W.lens.i(), d_z, Te, yl, d_logp, B, s);
+  glow_search(c, d_logp, W.lens.i(), yl, max_xlen, B, Tx, Te);
+  launch_glow_align_out(W.om.f(), C, Tx, W.lens.i(), W.xof.i(), Te, yl, d_ymean, d_attn, d_oattn_dur, B, s);
+  HIP_OK(hipMemcpyAsync(d_logw, W.logw.p, (size_t)B * Tx * 4, hipMemcpyDeviceToDevice, s));
+  HIP_OK(hipStreamSynchronize(s));
+}
+
+// maximum_path (monotonic_align/__init__.py:34-49) alone: d_logp (B, Tx, Ty) -> d_path (B, Tx, Ty)
+void glow_mas(tts_ctx* c, const float* d_logp, const int32_t* h_xlens, const int32_t* h_ylens, int B, int Tx, int Ty,
+              float* d_path) {
+  auto& W = c->glws;
+  TTS_CHECK(B >= 1 && B <= 64 && Tx >= 1 && Tx <= 4096 && Ty >= 1, "glow mas: bad sizes");
+  W.h_mxl.assign(h_xlens, h_xlens + B);  // staging vectors live in the workspace, as in glow_decode
+  W.h_myl.assign(h_ylens, h_ylens + B);
+  int max_xlen = 1;
+  for (int b = 0; b < B; ++b) {
+    const int xl = W.h_mxl[b], yl = W.h_myl[b];
+    TTS_CHECK(xl >= 1 && xl <= Tx && yl >= 1 && yl <= Ty, "glow mas: lengths out of range");
+    // below that the reference's search reads outside its band (core.pyx:18-35)
+    TTS_CHECK(yl >= xl, "glow mas: row " + std::to_string(b) + " has fewer frames than tokens");
+    max_xlen = std::max(max_xlen, xl);
+  }
+  long gen = 0;
+  grow<int>(W.mxl, 64, gen);
+  grow<int>(W.myl, 64, gen);
+  HIP_OK(hipMemcpyAsync(W.mxl.p, W.h_mxl.data(), B * 4, hipMemcpyHostToDevice, c->s));
+  HIP_OK(hipMemcpyAsync(W.myl.p, W.h_myl.data(), B * 4, hipMemcpyHostToDevice, c->s));
+  glow_search(c, d_logp, W.mxl.i(), W.myl.i(), max_xlen, B, Tx, Ty);
+  launch_glow_path(W.xof.i(), Tx, Ty, d_path, B, c->s);
+  HIP_OK(hipStreamSynchronize(c->s));
 }
 
 }  // namespace
@@ -535,6 +678,21 @@ int tts_glow_decode(tts_ctx* c, const float* d_noise, float noise_scale, int Ty,
   return ctx_call(
       c, stream, [&] { TTS_CHECK(c && d_y && d_ymean && d_attn && d_logw, "null argument"); },
       [&] { glow_decode(c, d_noise, noise_scale, Ty, d_y, d_ymean, d_attn, d_logw); });
+}
+
+int tts_glow_align(tts_ctx* c, const float* d_y, const int32_t* h_ylens, int Ty, float* d_z, float* d_logdet,
+                   float* d_logp, float* d_attn, float* d_ymean, float* d_oattn_dur, float* d_logw, void* stream) {
+  return ctx_call(
+      c, stream,
+      [&] { TTS_CHECK(c && d_y && h_ylens && d_z && d_logdet && d_attn && d_ymean && d_oattn_dur && d_logw, "null argument"); },
+      [&] { glow_align(c, d_y, h_ylens, Ty, d_z, d_logdet, d_logp, d_attn, d_ymean, d_oattn_dur, d_logw); });
+}
+
+int tts_glow_mas(tts_ctx* c, const float* d_logp, const int32_t* h_xlens, const int32_t* h_ylens, int B, int Tx,
+                 int Ty, float* d_path, void* stream) {
+  return ctx_call(
+      c, stream, [&] { TTS_CHECK(c && d_logp && h_xlens && h_ylens && d_path, "null argument"); },
+      [&] { glow_mas(c, d_logp, h_xlens, h_ylens, B, Tx, Ty, d_path); });
 }
 
 }  // extern "C"

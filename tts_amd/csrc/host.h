@@ -291,6 +291,11 @@ struct GlowModel {
   // the inverse InvConvNear + ActNorm from invtab (2C x {w[4], bias, exp(-logs)})
   std::vector<ConvLayer> start, end;
   std::vector<DevBuf> invtab;
+  // forward direction (GlowTts.forward): per block 2C x {w[s'][0..3], actnorm bias, exp(actnorm logs)}
+  // for the ActNorm + InvConvNear ahead of the block, and the weight-only part of the
+  // log-determinant per squeezed frame, sum_k [sum_c actnorm.logs_k + logdet(W_k) * 2C / 4]
+  std::vector<DevBuf> fwdtab;
+  double fwd_logdet_frame = 0.0;
   std::vector<ConvLayer> wn_in, wn_rs;  // [block * wn_layers + i]
   // speaker conditioning (glow_tts.py:97-99,159-161; encoder.py:131-135; glow.py:87-91,119-130):
   // c_in channels of g padded to c_pad (multiple of 16); the duration predictor's conv_1 reads
@@ -308,6 +313,11 @@ struct GlowWS {
   DevBuf spk, ones, g, gcond;  // speaker ids, unit lengths, normalized g (B, c_pad), cond biases
   bool has_g = false;          // the last glow_encode was given speaker ids
   std::vector<int> h_ylens, h_klens, h_spk;
+  // GlowTts.forward (glow_align) and the stand-alone alignment search (glow_mas): even mel lengths,
+  // their halves, the end conv's plain output, log-determinant partials, the likelihood matrix, the
+  // search's decision words and the frame -> token map
+  DevBuf aylens, aklens, eo, ldpart, logp, masbits, xof, mxl, myl;
+  std::vector<int> h_xlens, h_aylens, h_aklens, h_mxl, h_myl;
 };
 
 // ParallelWaveGAN generator (TTS/vocoder/models/parallel_wavegan_generator.py, setup_generator's

@@ -1,5 +1,5 @@
 // Launchers and host packers of the kernel files that have no header of their own (encoder.hip,
-// glow.hip, pwgan.hip). Each is declared here only; the file that defines it includes this header,
+// glow.hip, glow_forward.hip, pwgan.hip). Each is declared here only; the file that defines it includes this header,
 // so the compiler checks the signature against the definition.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -36,6 +36,20 @@ void launch_glow_unsqueeze(const float* x, int C2, int K, const int* ylens, floa
 void launch_glow_speaker(const int* spk, const float* table, int c_in, int c_pad, float* g, int B, hipStream_t s);
 void launch_glow_embed(const int64_t* ids, int T, const float* table, int rows, int D, const int* lens, float* out,
                        int B, hipStream_t s);
+
+// glow_forward.hip (GlowTts.forward: forward flows, likelihood matrix, monotonic alignment search)
+void launch_glow_fwd_glue(const float* x, const float* eo, const float* tab, float* out, int C, int K,
+                          const int* klens, double* part, int B, hipStream_t s);
+void launch_glow_logdet(const double* part, int nblk, int tiles, int B, const int* klens, double wconst, float* logdet,
+                        hipStream_t s);
+void launch_glow_logp(const float* om, int C, int Tx, const int* xlens, const float* z, int Ty, const int* ylens,
+                      float* logp, int B, hipStream_t s);
+long glow_mas_bits_words(int Tx, int Ty);  // 64-bit decision words per utterance
+void launch_glow_mas(const float* logp, int Tx, int Ty, const int* xlens, const int* ylens, int max_xlen,
+                     unsigned long long* bits, int* xof, int B, hipStream_t s);
+void launch_glow_path(const int* xof, int Tx, int Ty, float* path, int B, hipStream_t s);
+void launch_glow_align_out(const float* om, int C, int Tx, const int* xlens, const int* xof, int Ty, const int* ylens,
+                           float* y_mean, float* attn, float* dur, int B, hipStream_t s);
 
 // pwgan.hip
 void launch_pw_upsample(const float* in, long ib, int Lin_max, const int* lens, int len_add, int in_mul, int s,

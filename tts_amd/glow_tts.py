@@ -1,4 +1,4 @@
-"""Drop-in ``GlowTts`` whose ``inference`` runs on MI355X through ``libttship.so``.
+"""Drop-in ``GlowTts`` whose ``inference`` and ``eval()``-mode ``forward`` run on MI355X through ``libttship.so``.
 
 Mirrors ``TTS/tts/models/glow_tts.py`` as ``setup_model`` builds it for the reference configs
 (``TTS/tts/utils/generic_utils.py:105-129``: transformer (6 layers, 2 heads) or time-depth-separable
@@ -71,8 +71,75 @@ class GlowTts(NativeModel):
     def store_inverse(self):  # the library inverts InvConvNear and folds weight norm at load
         pass
 
-    def forward(self, *args, **kwargs):
-        raise NotImplementedError("training forward is out of scope; use inference()")
+    @torch.no_grad()
+    def forward(self, x, x_lengths, y=None, y_lengths=None, attn=None, g=None):
+        """The analysis direction (``glow_tts.py:114-156``) in ``eval()``: text and a mel in, the latent
+        ``z`` of the forward flows, their ``logdet``, and the hard monotonic alignment with what follows
+        from it out, as the reference's 7-tuple ``(z, logdet, y_mean, y_log_scale, attn, o_dur_log,
+        o_attn_dur)``. ``y`` is (B, 80, Ty); ``y_lengths`` (default Ty per row) are rounded down to even
+        and the outputs hold ``2 * floor(Ty / 2)`` frames (``preprocess``). A passed ``attn`` is ignored,
+        as in the reference (``:131-132``). Row i equals the B = 1 call on that row's own lengths.
+        ``last_logp`` keeps the likelihood matrix (B, Tx, Ty_even) the alignment was searched on."""
+        if self.training:
+            raise NotImplementedError("training forward is out of scope; forward() runs in eval() only")
+        y_max_length = y.size(2)  # y=None fails here, as in the reference
+        spk = self._speaker_ids(g)
+        dev = self.device
+        eng = self._engine()
+        with eng.lock:  # encode and align share the context's Glow workspace
+            self._sync(eng)
+            x = torch.as_tensor(x).to(dev, torch.int64)
+            if x.dim() == 1:
+                x = x[None]
+            x = x.contiguous()
+            B, T = x.shape
+            lens = row_lengths(torch.as_tensor(x_lengths).reshape(-1), B, T, "x_lengths")
+            if B > 64:
+                raise ValueError("at most 64 utterances per call")
+            if spk is not None and len(spk) != B:
+                raise ValueError("g must hold one speaker id per utterance")
+            y = torch.as_tensor(y).to(dev, torch.float32).contiguous()
+            if y.dim() != 3 or y.shape[0] != B or y.shape[1] != 80:
+                raise ValueError("y must be (B, 80, Ty)")
+            ylens = np.full(B, y_max_length, np.int64) if y_lengths is None else \
+                np.asarray(torch.as_tensor(y_lengths).cpu(), np.int64).reshape(-1)
+            if len(ylens) != B or ylens.min() < 0 or ylens.max() > y_max_length:
+                raise ValueError("y_lengths must have B entries in [0, Ty]")
+            ylens = ylens // 2 * 2
+            for i in range(B):
+                if ylens[i] < max(2, lens[i]):
+                    raise ValueError(f"row {i}: {ylens[i]} mel frames (rounded down to even) cannot be aligned "
+                                     f"with {lens[i]} tokens; forward needs at least max(2, tokens) frames")
+            Te = y_max_length // 2 * 2
+            eng.glow_encode(x, lens, float(self.length_scale), spk)
+            z = torch.empty(B, 80, Te, device=dev)
+            logdet = torch.empty(B, device=dev)
+            logp = torch.empty(B, T, Te, device=dev)
+            y_mean = torch.empty(B, 80, Te, device=dev)
+            attn = torch.empty(B, Te, T, device=dev)
+            logw = torch.empty(B, 1, T, device=dev)
+            o_attn_dur = torch.empty(B, 1, T, device=dev)
+            eng.glow_align(y, ylens, z, logdet, logp, attn, y_mean, o_attn_dur, logw)
+        x_mask = (torch.arange(T, device=dev)[None] < torch.as_tensor(lens, device=dev)[:, None]).float()[:, None]
+        self.last_y_lengths = ylens.astype(np.int32)
+        self.last_logp = logp
+        return z, logdet, y_mean, torch.zeros_like(y_mean), attn, logw * x_mask, o_attn_dur
+
+    def _speaker_ids(self, g):
+        """``g`` as (B,) int64 speaker ids or None; the checks and failures of ``inference``."""
+        if g is not None:
+            if self.cfg.num_speakers <= 1:
+                raise AttributeError("'GlowTts' object has no attribute 'emb_g'")
+            if not self.cfg.c_in_channels:
+                raise AttributeError("'WN' object has no attribute 'cond_layer'")
+            spk = np.asarray(torch.as_tensor(g).cpu(), np.int64).reshape(-1)
+            if spk.min() < 0 or spk.max() >= self.cfg.num_speakers:
+                raise IndexError("index out of range in self")  # nn.Embedding's message
+            return spk
+        if self.cfg.c_in_channels:
+            raise RuntimeError(f"the duration predictor expects {192 + self.cfg.c_in_channels} input channels "
+                               "(c_in_channels > 0): pass g")
+        return None
 
     def _load(self, eng):
         c = self.cfg
