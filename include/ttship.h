@@ -13,6 +13,9 @@
  *   tts_taco_forward              <- Tacotron2.forward(text, text_lengths, mel_specs, mel_lengths) in eval():
  *                                    the teacher-forced decode (models/tacotron2.py:95-140,
  *                                    layers/tacotron2.py:300-333)
+ *   tts_taco_style_mel / _tokens  <- gst_layer(style_mel, speaker_embedding) / compute_gst with a token dict
+ *                                    (TTS/tts/layers/gst_layers.py, tacotron_abstract.py:184-203)
+ *   tts_taco_infer_style / tts_taco_forward_style <- the two calls above on a model with gst=True
  *   tts_taco_encoder              <- embedding + Encoder.inference (models/tacotron2.py:144-145,
  *                                    layers/tacotron2.py:112-119)
  *   tts_taco_postnet              <- Postnet + residual (models/tacotron2.py:159-160)
@@ -103,7 +106,7 @@ int tts_taco_infer(tts_ctx* ctx, const int64_t* d_ids, const int32_t* h_lens, in
    (TTS/tts/models/tacotron2.py:142-156; speaker vector concatenated to the encoder outputs,
    tacotron_abstract.py:213-217). Exactly one of d_spk_ids (int64 (B), rows of the learned
    speaker_embedding table) or d_spk_emb (float (B, spk_dim), external per-sample embeddings) is
-   non-null. At most 64 utterances per call, speaker vectors of at most 512 dims. Other arguments
+   non-null. At most 64 utterances per call, conditioning vectors of at most 1024 dims. Other arguments
    as tts_taco_infer. */
 int tts_taco_infer_spk(tts_ctx* ctx, const int64_t* d_ids, const int32_t* h_lens, int B, int T_max, int r,
                        const int32_t* h_max_steps, int S_cap, float stop_threshold, const int64_t* d_spk_ids,
@@ -128,6 +131,41 @@ int tts_taco_forward(tts_ctx* ctx, const int64_t* d_ids, const int32_t* h_lens, 
                      const float* d_mel, const int32_t* h_mel_lens, int M_max, const int64_t* d_spk_ids,
                      const float* d_spk_emb, float* d_dec, float* d_post, float* d_align, float* d_stop,
                      void* stream);
+
+/* ---- Global Style Tokens (TTS/tts/layers/gst_layers.py; tacotron_abstract.py:184-203) ----
+   A multi-speaker Tacotron2 loaded with gst_layer.* tensors concatenates a style vector of
+   gst_dim to every encoder output, in front of the speaker vector (models/tacotron2.py:147-155).
+   tts_taco_speaker_dim then reports gst_dim + the speaker vector's width (the conditioning
+   width); gst_dim is reported here. query_uses_speaker: the style attention's W_query has speaker
+   columns (gst_use_speaker_embedding with external embeddings). gst_dim 0: no gst_layer. */
+int tts_taco_gst_info(tts_ctx* ctx, int* gst_dim, int* num_tokens, int* query_uses_speaker);
+
+/* gst_layer(mel, speaker_embedding): reference encoder + style-token attention.
+   d_mel      (B, N_max, 80) float; row b holds h_lens[b] frames (1 <= h_lens[b] <= N_max <= 65536),
+              nothing past them is read; B <= 64
+   d_spk_emb  (B, Es) when query_uses_speaker, else NULL (ignored)
+   d_style    out (B, gst_dim). Row b equals the reference B=1 call on d_mel[b, :h_lens[b]], bit for
+              bit whatever batch it sits in. Stream-asynchronous. */
+int tts_taco_style_mel(tts_ctx* ctx, const float* d_mel, const int32_t* h_lens, int B, int N_max,
+                       const float* d_spk_emb, float* d_style, void* stream);
+
+/* compute_gst with a {token: weight} dict: d_style (gst_dim) = sum_i h_weights[i] W_value tanh(token
+   h_token_ids[i]), added in the order given (n <= 64; n = 0: zeros). An index outside
+   [0, num_tokens) is an error. */
+int tts_taco_style_tokens(tts_ctx* ctx, const int32_t* h_token_ids, const float* h_weights, int n, float* d_style,
+                          void* stream);
+
+/* tts_taco_infer_spk / tts_taco_forward with the rows' style vectors d_style (B, gst_dim), caller
+   row order; NULL = zeros (style_mel=None). A non-NULL d_style on a model without gst_layer is an
+   error. The older entries are these with NULL. */
+int tts_taco_infer_style(tts_ctx* ctx, const int64_t* d_ids, const int32_t* h_lens, int B, int T_max, int r,
+                         const int32_t* h_max_steps, int S_cap, float stop_threshold, const int64_t* d_spk_ids,
+                         const float* d_spk_emb, const float* d_style, float* d_dec, float* d_post, float* d_align,
+                         float* d_stop, int32_t* h_steps, int32_t* h_status, void* stream);
+int tts_taco_forward_style(tts_ctx* ctx, const int64_t* d_ids, const int32_t* h_lens, int B, int T_max, int r,
+                           const float* d_mel, const int32_t* h_mel_lens, int M_max, const int64_t* d_spk_ids,
+                           const float* d_spk_emb, const float* d_style, float* d_dec, float* d_post, float* d_align,
+                           float* d_stop, void* stream);
 
 /* Decoder options that no tensor reveals (layers/tacotron2.py:147-200 -> common_layers.py:196-372):
    attention windowing at inference (attn_win) and forward attention (forward_attn; the transition

@@ -41,6 +41,14 @@ SIGNATURES = [
                                           _c_int_p, _vp]),
     ("tts_taco_forward", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _c_int_p,
                                         ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("tts_taco_gst_info", ctypes.c_int, [_vp, _c_i_p, _c_i_p, _c_i_p]),
+    ("tts_taco_style_mel", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
+    ("tts_taco_style_tokens", ctypes.c_int, [_vp, _c_int_p, _c_f_p, ctypes.c_int, _vp, _vp]),
+    ("tts_taco_infer_style", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_int_p,
+                                            ctypes.c_int, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int_p,
+                                            _c_int_p, _vp]),
+    ("tts_taco_forward_style", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
+                                              _c_int_p, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("tts_taco_mbmelgan_infer", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                _c_int_p, ctypes.c_int, ctypes.c_float, _vp, _vp, _vp, _vp, _vp,
                                                _vp, ctypes.c_int, _vp, _c_int_p, _c_int_p, _vp]),
@@ -206,10 +214,15 @@ class Engine:
                 (steps.ctypes.data_as(_c_int_p), status.ctypes.data_as(_c_int_p)), (lens_a, ms_a))
 
     def taco_infer(self, ids, lens, r, max_steps, S_cap, stop_threshold, dec, post, align, stop,
-                   speaker_ids=None, speaker_embeddings=None):
+                   speaker_ids=None, speaker_embeddings=None, style=None):
+        """``style``: (B, gst_dim) style vectors of a GST model (tts_taco_infer_style), None = zeros."""
         head, steps, status, res, keep = self._decode_args(ids, lens, r, max_steps, S_cap)
         outs = (_ptr(dec), _ptr(post), _ptr(align), _ptr(stop))
-        if speaker_ids is None and speaker_embeddings is None:
+        if style is not None:
+            _check(self.lib.tts_taco_infer_style(*head, float(stop_threshold), _opt_ptr(speaker_ids),
+                                                 _opt_ptr(speaker_embeddings), _ptr(style), *outs, *res,
+                                                 _stream(ids.device)))
+        elif speaker_ids is None and speaker_embeddings is None:
             _check(self.lib.tts_taco_infer(*head, float(stop_threshold), *outs, *res, _stream(ids.device)))
         else:
             _check(self.lib.tts_taco_infer_spk(*head, float(stop_threshold), _opt_ptr(speaker_ids),
@@ -217,15 +230,41 @@ class Engine:
         return steps, status
 
     def taco_forward(self, ids, lens, r, mel, mel_lens, dec, post, align, stop, speaker_ids=None,
-                     speaker_embeddings=None):
+                     speaker_embeddings=None, style=None):
         """Teacher-forced Tacotron2.forward in eval (tts_taco_forward): ``mel`` (B, M, 80) contiguous
-        fp32 with M a multiple of r; dec / post (B, M, 80), align (B, M / r, T), stop (B, M / r)."""
+        fp32 with M a multiple of r; dec / post (B, M, 80), align (B, M / r, T), stop (B, M / r).
+        ``style``: (B, gst_dim) style vectors of a GST model (tts_taco_forward_style)."""
         B, T = ids.shape
         lens_a, lens_p = _i32(lens)
         ml_a, ml_p = _i32(mel_lens)
-        _check(self.lib.tts_taco_forward(self.h, _ptr(ids), lens_p, B, T, r, _ptr(mel), ml_p, int(mel.shape[1]),
-                                         _opt_ptr(speaker_ids), _opt_ptr(speaker_embeddings), _ptr(dec), _ptr(post),
-                                         _ptr(align), _ptr(stop), _stream(ids.device)))
+        head = (self.h, _ptr(ids), lens_p, B, T, r, _ptr(mel), ml_p, int(mel.shape[1]), _opt_ptr(speaker_ids),
+                _opt_ptr(speaker_embeddings))
+        tail = (_ptr(dec), _ptr(post), _ptr(align), _ptr(stop), _stream(ids.device))
+        if style is not None:
+            _check(self.lib.tts_taco_forward_style(*head, _ptr(style), *tail))
+        else:
+            _check(self.lib.tts_taco_forward(*head, *tail))
+
+    def taco_gst_info(self):
+        """(gst_dim, num_tokens, query_uses_speaker) of the loaded Tacotron2 (tts_taco_gst_info)."""
+        g, n, q = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        _check(self.lib.tts_taco_gst_info(self.h, ctypes.byref(g), ctypes.byref(n), ctypes.byref(q)))
+        return g.value, n.value, bool(q.value)
+
+    def taco_style_mel(self, mel, lens, speaker_embeddings, style):
+        """Style vectors of mels (tts_taco_style_mel): ``mel`` (B, N, 80) contiguous fp32, ``lens`` the
+        rows' frame counts, ``speaker_embeddings`` (B, Es) or None -> ``style`` (B, gst_dim)."""
+        B, N, _ = mel.shape
+        lens_a, lens_p = _i32(lens)
+        _check(self.lib.tts_taco_style_mel(self.h, _ptr(mel), lens_p, B, N, _opt_ptr(speaker_embeddings),
+                                           _ptr(style), _stream(mel.device)))
+
+    def taco_style_tokens(self, token_ids, weights, style):
+        """Style vector of a {token: weight} dict (tts_taco_style_tokens) -> ``style`` (gst_dim)."""
+        ids_a, ids_p = _i32(token_ids)
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32))
+        _check(self.lib.tts_taco_style_tokens(self.h, ids_p, w.ctypes.data_as(_c_f_p), len(ids_a), _ptr(style),
+                                              _stream(style.device)))
 
     def taco_mbmelgan_infer(self, ids, lens, r, max_steps, S_cap, stop_threshold, dec, post, align, stop, pad, wav,
                             speaker_ids=None, speaker_embeddings=None):

@@ -7,6 +7,7 @@
 #include "split16.h"
 #include "switches.h"
 
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 
@@ -585,7 +586,7 @@ void stage_row_biases(tts_ctx* c, const PArgs& a, hipStream_t s) {
   const int N = a.spk_ld, pj0 = (int)(a.pjb_rows - W.spkb.f()), Bp = W.MT * 16;
   TTS_CHECK(W.B <= SPK_BMAX || !M.spk_dim, "multi-speaker decoding: at most 64 utterances per call");
   const int Bs = M.spk_dim ? W.B : 0;
-  TTS_CHECK(M.spk_dim <= 512, "speaker vectors of at most 512 dims");
+  TTS_CHECK(M.spk_dim <= 1024, "conditioning vectors ([style | speaker]) of at most 1024 dims");
   const float* wt = M.spk_dim ? M.spk_wT.f() : nullptr;
   const int es = M.spk_dim, p0 = a.spk_scale ? N : pj0;
   const dim3 g((N + 63) / 64);
@@ -735,21 +736,39 @@ std::vector<int> stage_decode_order(tts_ctx* c, const int32_t* h_lens, const int
   return perm;
 }
 
-// speaker vectors in decode order: external embeddings, or rows of the learned table
-void stage_speakers(tts_ctx* c, const int64_t* d_spk_ids, const float* d_spk_emb, int B, hipStream_t s) {
+// GST models: decode row i's conditioning vector [style of caller row map[i] (zeros without one) | speaker i]
+__global__ void gst_cond_kernel(const float* __restrict__ style, const int* __restrict__ map,
+                                const float* __restrict__ spk, int G, int Es, float* __restrict__ out) {
+  const int i = blockIdx.x;
+  const float* st = style ? style + (long)map[i] * G : nullptr;
+  for (int e = threadIdx.x; e < G + Es; e += blockDim.x)
+    out[(long)i * (G + Es) + e] = e < G ? (st ? st[e] : 0.f) : spk[(long)i * Es + e - G];
+}
+
+// conditioning vectors in decode order: the speaker vectors (external embeddings, or rows of the
+// learned table), behind the style vectors when the model has GST
+void stage_speakers(tts_ctx* c, const int64_t* d_spk_ids, const float* d_spk_emb, const float* d_style, int B,
+                    hipStream_t s) {
   auto& M = c->taco;
   auto& W = c->tws;
+  TTS_CHECK(!d_style || M.gst_dim, "a style vector was given, but the model has no gst_layer");
   if (!M.spk_dim) return;
+  if (M.gst_dim) grow<float>(W.spk_only, (size_t)64 * 1024, W.gen);
+  float* spk_out = M.gst_dim ? W.spk_only.f() : W.spk.f();
   TTS_CHECK(d_spk_ids || d_spk_emb, "multi-speaker model: speaker ids or speaker embeddings are required");
   TTS_CHECK(use_persistent(c), "multi-speaker decoding runs on the persistent decoder only (<= 64 utterances "
                                "per call on a 256-CU device)");
   if (d_spk_emb) {
-    gather_rows<float>(d_spk_emb, W.spk.f(), W.map.i(), M.spk_dim, B, s);
+    gather_rows<float>(d_spk_emb, spk_out, W.map.i(), M.es, B, s);
   } else {
     TTS_CHECK(M.num_spk > 0, "model has no speaker_embedding table: pass speaker embeddings");
     gather_rows<int64_t>(d_spk_ids, reinterpret_cast<int64_t*>(W.spkid.p), W.map.i(), 1, B, s);
-    launch_embed_gather(reinterpret_cast<const int64_t*>(W.spkid.p), 1, M.spk_table.f(), M.num_spk, M.spk_dim,
-                        W.lens.i(), B, W.spk.f(), s);
+    launch_embed_gather(reinterpret_cast<const int64_t*>(W.spkid.p), 1, M.spk_table.f(), M.num_spk, M.es,
+                        W.lens.i(), B, spk_out, s);
+  }
+  if (M.gst_dim) {
+    gst_cond_kernel<<<B, 256, 0, s>>>(d_style, W.map.i(), spk_out, M.gst_dim, M.es, W.spk.f());
+    HIP_OK(hipGetLastError());
   }
 }
 
@@ -901,7 +920,7 @@ void report_rows(tts_ctx* c, const std::vector<int>& perm, int32_t* h_steps, int
 void ttsh::taco_infer(tts_ctx* c, const int64_t* ids, const int32_t* h_lens, int B, int T_max, int r,
                 const int32_t* h_max_steps, int S_cap, float thr, float* d_dec, float* d_post, float* d_align,
                 float* d_stop, int32_t* h_steps, int32_t* h_status, void* stream,
-                const int64_t* d_spk_ids, const float* d_spk_emb, const FusedVoc* fv) {
+                const int64_t* d_spk_ids, const float* d_spk_emb, const FusedVoc* fv, const float* d_style) {
   const int max_ms = check_infer_args(c->taco, h_lens, B, T_max, r, h_max_steps, S_cap);
   taco_workspace(c, B, T_max, S_cap, r);
   auto& W = c->tws;
@@ -914,7 +933,7 @@ void ttsh::taco_infer(tts_ctx* c, const int64_t* ids, const int32_t* h_lens, int
   TTS_CHECK(!c->taco.variant() || persist, "BN prenet / attention windowing / forward / Graves attention run on "
                                            "the persistent decoder only (<= 64 utterances per call on a 256-CU "
                                            "device)");
-  stage_speakers(c, d_spk_ids, d_spk_emb, B, s);
+  stage_speakers(c, d_spk_ids, d_spk_emb, d_style, B, s);
   run_encoder_penc(c, ids, B, T_max, s);
   if (persist && !W.pslot_cal) {  // ordered after the caller's work (enter above) and this call's encoder
     pick_barrier_blocks(reinterpret_cast<unsigned*>(W.pbar.p), PBAR_CAND, PMAX_LAUNCH, W.pslot, s);
@@ -943,7 +962,7 @@ void ttsh::taco_infer(tts_ctx* c, const int64_t* ids, const int32_t* h_lens, int
 void ttsh::taco_forward(tts_ctx* c, const int64_t* ids, const int32_t* h_lens, int B, int T_max, int r,
                         const float* d_mel, const int32_t* h_mel_lens, int M_max, const int64_t* d_spk_ids,
                         const float* d_spk_emb, float* d_dec, float* d_post, float* d_align, float* d_stop,
-                        void* stream) {
+                        void* stream, const float* d_style) {
   auto& M = c->taco;
   TTS_CHECK(M.ready, "tacotron2 weights not finalized");
   TTS_CHECK(M_max >= 1 && M_max <= (1 << 20) && r >= 1 && M_max % r == 0, "M_max must be a positive multiple of r");
@@ -966,7 +985,7 @@ void ttsh::taco_forward(tts_ctx* c, const int64_t* ids, const int32_t* h_lens, i
   W.thr = 0.5f;  // unused: a teacher-forced row never stops by its stop token
   TTS_CHECK(use_persistent(c), "teacher-forced forward runs on the persistent decoder only (<= 64 utterances per "
                                "call on a 256-CU device, TTS_DECODER=graph unset)");
-  stage_speakers(c, d_spk_ids, d_spk_emb, B, s);
+  stage_speakers(c, d_spk_ids, d_spk_emb, d_style, B, s);
   run_encoder_penc(c, ids, B, T_max, s);
   if (!W.pslot_cal) {
     pick_barrier_blocks(reinterpret_cast<unsigned*>(W.pbar.p), PBAR_CAND, PMAX_LAUNCH, W.pslot, s);
@@ -1007,13 +1026,92 @@ int tts_taco_forward(tts_ctx* c, const int64_t* d_ids, const int32_t* h_lens, in
                      const float* d_mel, const int32_t* h_mel_lens, int M_max, const int64_t* d_spk_ids,
                      const float* d_spk_emb, float* d_dec, float* d_post, float* d_align, float* d_stop,
                      void* stream) {
+  return tts_taco_forward_style(c, d_ids, h_lens, B, T_max, r, d_mel, h_mel_lens, M_max, d_spk_ids, d_spk_emb, nullptr,
+                                d_dec, d_post, d_align, d_stop, stream);
+}
+
+int tts_taco_forward_style(tts_ctx* c, const int64_t* d_ids, const int32_t* h_lens, int B, int T_max, int r,
+                           const float* d_mel, const int32_t* h_mel_lens, int M_max, const int64_t* d_spk_ids,
+                           const float* d_spk_emb, const float* d_style, float* d_dec, float* d_post, float* d_align,
+                           float* d_stop, void* stream) {
   return guarded_ctx(c, [&] {
     TTS_CHECK(c && d_ids && h_lens && d_mel && h_mel_lens && d_dec && d_post && d_align && d_stop, "null argument");
     DeviceGuard g(c->device);
     with_x3_fallback(c, [&] {
       taco_forward(c, d_ids, h_lens, B, T_max, r, d_mel, h_mel_lens, M_max, d_spk_ids, d_spk_emb, d_dec, d_post,
-                   d_align, d_stop, stream);
+                   d_align, d_stop, stream, d_style);
     });
+  });
+}
+
+int tts_taco_gst_info(tts_ctx* c, int* gst_dim, int* num_tokens, int* query_uses_speaker) {
+  return guarded_ctx(c, [&] {
+    TTS_CHECK(gst_dim && num_tokens && query_uses_speaker, "null argument");
+    TTS_CHECK(c->taco.ready, "tacotron2 weights not finalized");
+    *gst_dim = c->taco.gst_dim;
+    *num_tokens = c->taco.gst_dim ? c->taco.gst_ntok : 0;
+    *query_uses_speaker = c->taco.gst_dim && c->taco.gst_es_q ? 1 : 0;
+  });
+}
+
+int tts_taco_style_mel(tts_ctx* c, const float* d_mel, const int32_t* h_lens, int B, int N_max, const float* d_spk_emb,
+                       float* d_style, void* stream) {
+  return guarded_ctx(c, [&] {
+    auto& M = c->taco;
+    TTS_CHECK(d_mel && h_lens && d_style, "null argument");
+    TTS_CHECK(M.ready && M.gst_dim, "the loaded tacotron2 model has no gst_layer");
+    TTS_CHECK(B >= 1 && B <= BMAX, "B must be in [1, 64]");
+    TTS_CHECK(N_max >= 1 && N_max <= (1 << 16), "N_max must be in [1, 65536]");
+    TTS_CHECK(!M.gst_es_q || d_spk_emb, "this model's style query takes the speaker embeddings: pass them");
+    GstLens lens{};
+    for (int b = 0; b < B; ++b) {
+      TTS_CHECK(h_lens[b] >= 1 && h_lens[b] <= N_max, "style mel lens out of range");
+      lens.v[b] = h_lens[b];
+    }
+    DeviceGuard g(c->device);
+    // layer 1's output (B, W1, 40, 32) and layer 2's (B, W2, 20, 32); the later, smaller layers alternate
+    const int W1 = (N_max + 1) / 2, W2 = (W1 + 1) / 2;
+    int W6 = W2;
+    for (int l = 2; l < 6; ++l) W6 = (W6 + 1) / 2;
+    c->gstws.a.ensure((size_t)B * W1 * 40 * 32 * 4);
+    c->gstws.b.ensure((size_t)B * W2 * 20 * 32 * 4);
+    enter(c, stream);
+    const float *cw[6], *cb[6];
+    for (int l = 0; l < 6; ++l) cw[l] = M.gst_cw[l].f(), cb[l] = M.gst_cb[l].f();
+    launch_gst_convs(d_mel, lens, B, N_max, cw, cb, c->gstws.a.f(), c->gstws.b.f(), c->s);
+    GstHeadArgs a{};
+    a.x = c->gstws.b.f();
+    a.xb = (long)W6 * 256;
+    a.lens = lens;
+    a.wihT = M.gst_wihT.f(), a.whhT = M.gst_whhT.f(), a.bih = M.gst_bih.f(), a.bhh = M.gst_bhh.f();
+    a.wqT = M.gst_wqT.f(), a.Kt = M.gst_K.f(), a.Vt = M.gst_V.f();
+    a.spk = M.gst_es_q ? d_spk_emb : nullptr;
+    a.Hg = M.gst_dim / 2, a.G = M.gst_dim, a.heads = M.gst_heads, a.ntok = M.gst_ntok, a.Es = M.gst_es_q;
+    a.scale = (float)std::sqrt((double)(M.gst_dim / M.gst_heads));
+    a.out = d_style;
+    launch_gst_head(a, B, c->s);
+    leave(c, stream);
+  });
+}
+
+int tts_taco_style_tokens(tts_ctx* c, const int32_t* h_token_ids, const float* h_weights, int n, float* d_style,
+                          void* stream) {
+  return guarded_ctx(c, [&] {
+    auto& M = c->taco;
+    TTS_CHECK(d_style && (n == 0 || (h_token_ids && h_weights)), "null argument");
+    TTS_CHECK(M.ready && M.gst_dim, "the loaded tacotron2 model has no gst_layer");
+    TTS_CHECK(n >= 0 && n <= GST_DICT_MAX, "at most 64 token weights");
+    GstTokenArgs a{};
+    a.n = n;
+    for (int i = 0; i < n; ++i) {
+      TTS_CHECK(h_token_ids[i] >= 0 && h_token_ids[i] < M.gst_ntok, "style token index out of range");
+      a.id[i] = h_token_ids[i];
+      a.w[i] = h_weights[i];
+    }
+    DeviceGuard g(c->device);
+    enter(c, stream);
+    launch_gst_tokens(a, M.gst_V.f(), M.gst_dim, M.gst_ntok, d_style, c->s);
+    leave(c, stream);
   });
 }
 
@@ -1028,13 +1126,21 @@ int tts_taco_infer_spk(tts_ctx* c, const int64_t* d_ids, const int32_t* h_lens, 
                        const int32_t* h_max_steps, int S_cap, float thr, const int64_t* d_spk_ids,
                        const float* d_spk_emb, float* d_dec, float* d_post, float* d_align, float* d_stop,
                        int32_t* h_steps, int32_t* h_status, void* stream) {
+  return tts_taco_infer_style(c, d_ids, h_lens, B, T_max, r, h_max_steps, S_cap, thr, d_spk_ids, d_spk_emb, nullptr,
+                              d_dec, d_post, d_align, d_stop, h_steps, h_status, stream);
+}
+
+int tts_taco_infer_style(tts_ctx* c, const int64_t* d_ids, const int32_t* h_lens, int B, int T_max, int r,
+                         const int32_t* h_max_steps, int S_cap, float thr, const int64_t* d_spk_ids,
+                         const float* d_spk_emb, const float* d_style, float* d_dec, float* d_post, float* d_align,
+                         float* d_stop, int32_t* h_steps, int32_t* h_status, void* stream) {
   return guarded_ctx(c, [&] {
     TTS_CHECK(c && d_ids && h_lens && h_max_steps && d_dec && d_post && d_align && d_stop && h_steps && h_status,
               "null argument");
     DeviceGuard g(c->device);
     with_x3_fallback(c, [&] {
       taco_infer(c, d_ids, h_lens, B, T_max, r, h_max_steps, S_cap, thr, d_dec, d_post, d_align, d_stop, h_steps,
-                 h_status, stream, d_spk_ids, d_spk_emb);
+                 h_status, stream, d_spk_ids, d_spk_emb, nullptr, d_style);
     });
   });
 }

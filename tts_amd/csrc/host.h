@@ -163,6 +163,17 @@ struct TacoModel {
   DevBuf spk_table;  // speaker_embedding.weight (num_spk, 512) when learned
   std::vector<float> spk_att_h, spk_dec_h, spk_penc_h, proj_spk;
   DevBuf spk_wT;
+  // Global Style Tokens (gst.hip; gst_layer.* present): the style vector of gst_dim sits in front of
+  // the speaker vector in the decoder's input, so spk_dim = gst_dim + es is the conditioning width
+  // and the per-row bias fold takes [style | speaker]. es = the speaker vector's own width.
+  int gst_dim = 0, gst_heads = 0, gst_ntok = 0, gst_es_q = 0, es = 0;
+  DevBuf gst_cw[6], gst_cb[6];  // reference-encoder convs [3][3][Cin][Cout], BatchNorm folded
+  DevBuf gst_wihT, gst_whhT, gst_bih, gst_bhh, gst_wqT, gst_K, gst_V;
+};
+
+// style encoder workspace: the conv layers' ping-pong buffers (tts_taco_style_mel)
+struct GstWS {
+  DevBuf a, b;
 };
 
 // Tacotron2 status words (TacoWS::stat on the device, tts_ctx::pinned on the host; one copy after
@@ -203,7 +214,8 @@ struct TacoWS {
   const void* pslot_base = nullptr;
   bool pslot_cal = false;      // pslot timed (after enter(), on the first persistent decode of these blocks)
   DevBuf anorm;                // persistent decoder: per-utterance attention normaliser (deferred alignment)
-  DevBuf spk, spkid, spkb;     // speaker vectors (decode order), per-row biases [Bp][NSPK]
+  DevBuf spk, spkid, spkb;     // conditioning vectors (decode order), per-row biases [Bp][NSPK]
+  DevBuf spk_only;             // GST models: the speaker vectors alone, before [style | speaker] is built
   DevBuf win_idx, fwd_u, apf;  // windowing argmax, transition probability, forward chunk sums
   DevBuf gh, gmu;              // Graves: N_a hidden (32 x 1024), mixture means (64 x 16)
   DevBuf teach;                // teacher-forced decode: prenet layer 1 of the ground-truth frames [S_cap][Bp][256]
@@ -408,6 +420,7 @@ struct tts_ctx {
   ttsh::HostMap taco_host, mg_host;
   ttsh::TacoModel taco;
   ttsh::TacoWS tws;
+  ttsh::GstWS gstws;
   ttsh::MelganModel mg;
   ttsh::MelganWS mws;
   ttsh::HostMap ge2e_host;
@@ -576,12 +589,17 @@ struct FusedVoc {
 void taco_infer(tts_ctx* c, const int64_t* ids, const int32_t* h_lens, int B, int T_max, int r,
                 const int32_t* h_max_steps, int S_cap, float thr, float* d_dec, float* d_post, float* d_align,
                 float* d_stop, int32_t* h_steps, int32_t* h_status, void* stream,
-                const int64_t* d_spk_ids = nullptr, const float* d_spk_emb = nullptr, const FusedVoc* fv = nullptr);
+                const int64_t* d_spk_ids = nullptr, const float* d_spk_emb = nullptr, const FusedVoc* fv = nullptr,
+                const float* d_style = nullptr);
 
 // Tacotron2.forward in eval (tts_taco_forward): d_mel (B, M_max, 80), M_max a multiple of r
 void taco_forward(tts_ctx* c, const int64_t* ids, const int32_t* h_lens, int B, int T_max, int r, const float* d_mel,
                   const int32_t* h_mel_lens, int M_max, const int64_t* d_spk_ids, const float* d_spk_emb, float* d_dec,
-                  float* d_post, float* d_align, float* d_stop, void* stream);
+                  float* d_post, float* d_align, float* d_stop, void* stream, const float* d_style = nullptr);
+// d_style (B, gst_dim), caller row order, or null (zeros): GST models only
+
+// Global Style Tokens, load: gst_layer.* folded and uploaded, key / value tables built (api_taco_load.hip)
+void gst_load(tts_ctx* c);
 
 // --- MelGAN: api_melgan.hip, for the fused path
 // returns total upsampling factor; writes bands (B, out_ch, up*(M_max+2pad)) into `out`

@@ -111,6 +111,38 @@ struct T1DecArgs {
 };
 void launch_t1_decoder(const T1DecArgs& a, int B, hipStream_t s);
 
+// gst.hip (Global Style Tokens). Row lengths (mel frames) travel as a kernel argument.
+constexpr int GST_HG_MAX = 256, GST_G_MAX = 512, GST_ES_MAX = 1024, GST_HEADS_MAX = 8, GST_TOK_MAX = 32,
+              GST_DICT_MAX = 64;
+struct GstLens {
+  int v[64];
+};
+// the six reference-encoder layers: mel (B, N_max, 80) -> bufB (B, W6, 2, 128), W_l = ceil(W_{l-1} / 2)
+// of N_max; W[l] is [3][3][Cin][Cout] with BatchNorm folded, bias[l] the folded bias. bufA holds
+// layer 1's output (B, W1, 40, 32), bufB layer 2's (B, W2, 20, 32); later layers alternate.
+void launch_gst_convs(const float* mel, const GstLens& lens, int B, int N_max, const float* const* W,
+                      const float* const* bias, float* bufA, float* bufB, hipStream_t s);
+// GRU over x (B, W6, 256) ([mel bin][channel] features), then the style-token attention -> out (B, G).
+// wihT [256][3 Hg], whhT [Hg][3 Hg] (gates r | z | n), wqT [Hg + Es][G], Kt / Vt [ntok][G];
+// spk (B, Es) when the query takes the speaker embedding (Es > 0); scale = sqrt(G / heads)
+struct GstHeadArgs {
+  const float* x;
+  long xb;
+  GstLens lens;
+  const float *wihT, *whhT, *bih, *bhh, *wqT, *Kt, *Vt, *spk;
+  int Hg, G, heads, ntok, Es;
+  float scale;
+  float* out;
+};
+void launch_gst_head(const GstHeadArgs& a, int B, hipStream_t s);
+// out (G) = sum_i w[i] Vt[id[i]] in the order given
+struct GstTokenArgs {
+  int n;
+  int id[GST_DICT_MAX];
+  float w[GST_DICT_MAX];
+};
+void launch_gst_tokens(const GstTokenArgs& a, const float* Vt, int G, int ntok, float* out, hipStream_t s);
+
 // griffin_lim.hip. Row lengths travel as a kernel argument (at most 64 rows), so a call needs no
 // host-to-device copy. W = e^{-2 pi i m / 1024} (1024 complex), win = the window zero-padded to
 // 1024, nonzero inside [wlo, whi); env (B, env_stride) the rows' window-square envelopes; F

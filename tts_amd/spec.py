@@ -56,6 +56,13 @@ class TacotronConfig:
     attn_type: str = "original"     # or "graves" (GravesAttention, common_layers.py:113-193)
     bidirectional_decoder: bool = False  # decoder_backward: a training-time copy, unused at inference
     attn_K: int = 5                 # Graves mixture components
+    # Global Style Tokens (tacotron_abstract.py:83-86, models/tacotron2.py:71-77, gst_layers.py): a
+    # style vector of gst_embedding_dim concatenated to every encoder output, before the speaker vector
+    gst: bool = False
+    gst_embedding_dim: int = 512
+    gst_num_heads: int = 4
+    gst_style_tokens: int = 10
+    gst_use_speaker_embedding: bool = False  # the query takes the per-sample speaker embedding too
 
     @property
     def spk_dim(self) -> int:
@@ -64,9 +71,21 @@ class TacotronConfig:
         return 512 if self.speaker_embedding_dim is None else int(self.speaker_embedding_dim)
 
     @property
+    def gst_dim(self) -> int:
+        return int(self.gst_embedding_dim) if self.gst else 0
+
+    @property
+    def gst_query_speaker_dim(self) -> int:
+        """Speaker columns of the style attention's W_query (models/tacotron2.py:77)."""
+        if self.gst and self.gst_use_speaker_embedding and self.num_speakers > 1 and \
+                self.speaker_embedding_dim is not None:
+            return int(self.speaker_embedding_dim)
+        return 0
+
+    @property
     def decoder_in(self) -> int:
-        """decoder_in_features (models/tacotron2.py:57-58)."""
-        return self.encoder_dim + self.spk_dim
+        """decoder_in_features (tacotron_abstract.py:85, models/tacotron2.py:57-58)."""
+        return self.encoder_dim + self.gst_dim + self.spk_dim
 
 
 @dataclass
@@ -150,8 +169,34 @@ def _decoder(prefix: str, c: TacotronConfig, r: int) -> Spec:
     return s
 
 
+GST_FILTERS = (1, 32, 32, 64, 64, 128, 128)  # ReferenceEncoder conv channels (gst_layers.py:38)
+
+
+def _gst(prefix: str, c: TacotronConfig) -> Spec:
+    """``GST`` (gst_layers.py:6-176): ReferenceEncoder (6 x Conv2d 3x3 stride 2 + BatchNorm2d, GRU on
+    128 channels x 2 mel bins) and StyleTokenLayer (tokens + multi-head attention without biases)."""
+    G, dk = c.gst_embedding_dim, c.gst_embedding_dim // c.gst_num_heads
+    s: Spec = []
+    for i in range(6):
+        s += [(f"{prefix}.encoder.convs.{i}.weight", (GST_FILTERS[i + 1], GST_FILTERS[i], 3, 3), "conv"),
+              (f"{prefix}.encoder.convs.{i}.bias", (GST_FILTERS[i + 1],), "bias")]
+    for i in range(6):
+        bn, n = f"{prefix}.encoder.bns.{i}", GST_FILTERS[i + 1]
+        s += [(f"{bn}.weight", (n,), "bn_w"), (f"{bn}.bias", (n,), "bn_b"), (f"{bn}.running_mean", (n,), "bn_mean"),
+              (f"{bn}.running_var", (n,), "bn_var"), (f"{bn}.num_batches_tracked", (), "count")]
+    s += [(f"{prefix}.encoder.recurrence.weight_ih_l0", (3 * (G // 2), 256), "gst_gru"),
+          (f"{prefix}.encoder.recurrence.weight_hh_l0", (3 * (G // 2), G // 2), "gst_gru"),
+          (f"{prefix}.encoder.recurrence.bias_ih_l0", (3 * (G // 2),), "gst_gru"),
+          (f"{prefix}.encoder.recurrence.bias_hh_l0", (3 * (G // 2),), "gst_gru"),
+          (f"{prefix}.style_token_layer.style_tokens", (c.gst_style_tokens, dk), "gst_tokens"),
+          (f"{prefix}.style_token_layer.attention.W_query.weight", (G, G // 2 + c.gst_query_speaker_dim), "gst_attn"),
+          (f"{prefix}.style_token_layer.attention.W_key.weight", (G, dk), "gst_attn"),
+          (f"{prefix}.style_token_layer.attention.W_value.weight", (G, dk), "gst_attn")]
+    return s
+
+
 def tacotron2_spec(c: TacotronConfig) -> Spec:
-    """Ordered state_dict spec of ``Tacotron2`` (no GST)."""
+    """Ordered state_dict spec of ``Tacotron2``."""
     E = c.encoder_dim
     s: Spec = []
     if c.num_speakers > 1 and c.speaker_embedding_dim is None:
@@ -172,6 +217,8 @@ def tacotron2_spec(c: TacotronConfig) -> Spec:
     chans = [F, 512, 512, 512, 512, F]
     for i in range(5):
         s += _conv_bn(f"postnet.convolutions.{i}", chans[i], chans[i + 1], 5)
+    if c.gst:  # models/tacotron2.py:72-77, registered after the postnet
+        s += _gst("gst_layer", c)
     if c.bidirectional_decoder:  # tacotron_abstract.py:104-105 (deepcopy of the decoder)
         s += _decoder("decoder_backward", c, c.r)
     if c.double_decoder_consistency:

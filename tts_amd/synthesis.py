@@ -41,6 +41,13 @@ def embedding_to_torch(speaker_embedding, cuda=False):
     return speaker_embedding
 
 
+def compute_style_mel(style_wav, ap, cuda=False):
+    """synthesis.py:40-45: the melspectrogram as (1, num_mels, N), untransposed -- the model reads its
+    memory as rows of 80 values, as the reference's ``inputs.view`` does (gst_layers.py:63)."""
+    style_mel = torch.FloatTensor(ap.melspectrogram(ap.load_wav(style_wav, sr=ap.sample_rate))).unsqueeze(0)
+    return style_mel.cuda() if cuda else style_mel
+
+
 def _get(c, k, default=None):
     try:
         return c[k]
@@ -101,8 +108,9 @@ def synthesis(model, text, CONFIG, use_cuda, ap, speaker_id=None, style_wav=None
     """synthesis.py:178-262 (torch backend)."""
     if backend != "torch":
         raise NotImplementedError("the TF / TFLite backends are outside the MI355X build")
-    if _get(CONFIG, "use_gst", False) and style_wav is not None:
-        raise NotImplementedError("GST style conditioning is outside the MI355X hot path (SURVEY.md §2)")
+    style_mel = None
+    if _get(CONFIG, "use_gst", False) and style_wav is not None:  # synthesis.py:209-214: a token dict passes through
+        style_mel = style_wav if isinstance(style_wav, dict) else compute_style_mel(style_wav, ap, cuda=use_cuda)
     inputs = text_to_seqvec(text, CONFIG, phonemize)
     if speaker_id is not None:
         speaker_id = id_to_torch(speaker_id, cuda=use_cuda)
@@ -110,7 +118,7 @@ def synthesis(model, text, CONFIG, use_cuda, ap, speaker_id=None, style_wav=None
         speaker_embedding = embedding_to_torch(speaker_embedding, cuda=use_cuda)
     inputs = numpy_to_torch(inputs, torch.long, cuda=use_cuda).unsqueeze(0)
     decoder_output, postnet_output, alignments, stop_tokens = run_model_torch(
-        model, inputs, CONFIG, truncated, speaker_id, None, speaker_embeddings=speaker_embedding)
+        model, inputs, CONFIG, truncated, speaker_id, style_mel, speaker_embeddings=speaker_embedding)
     postnet_output, decoder_output, alignment, stop_tokens = parse_outputs_torch(
         postnet_output, decoder_output, alignments, stop_tokens)
     wav = None

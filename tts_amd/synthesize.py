@@ -3,8 +3,9 @@
 printout). The model runs in ``libttship.so``; without a vocoder, Griffin-Lim on the CPU.
 
 Deliberate differences: ``--speaker_fileid`` may be omitted for a single-speaker model (the
-reference calls ``None.isdigit()`` there, ``synthesize.py:147-151``); GST style input is outside
-this build.
+reference calls ``None.isdigit()`` there, ``synthesize.py:147-151``). ``--gst_style`` is a JSON
+``{"token": weight}`` dict or the path of a style wav, for multi-speaker Tacotron2 models with
+``use_gst`` (``synthesize.py:155-164``).
 """
 
 import argparse
@@ -21,10 +22,11 @@ from .synthesis import synthesis
 from .text import make_symbols, phonemes, symbols
 
 
-def tts(model, vocoder_model, text, CONFIG, use_cuda, ap, use_gl, speaker_fileid, speaker_embedding=None):
+def tts(model, vocoder_model, text, CONFIG, use_cuda, ap, use_gl, speaker_fileid, speaker_embedding=None,
+        gst_style=None):
     """synthesize.py:21-43."""
     t_1 = time.time()
-    waveform, _, _, mel_postnet_spec, _, _ = synthesis(model, text, CONFIG, use_cuda, ap, speaker_fileid, None,
+    waveform, _, _, mel_postnet_spec, _, _ = synthesis(model, text, CONFIG, use_cuda, ap, speaker_fileid, gst_style,
                                                        False, CONFIG.get("enable_eos_bos_chars", False), use_gl,
                                                        speaker_embedding=speaker_embedding)
     if not use_gl:
@@ -36,6 +38,25 @@ def tts(model, vocoder_model, text, CONFIG, use_cuda, ap, use_gl, speaker_fileid
     print(" > Real-time factor: {}".format(rtf))
     print(" > Time per step: {}".format((time.time() - t_1) / len(waveform)))
     return waveform
+
+
+def parse_gst_style(arg, C):
+    """synthesize.py:155-164: no argument -> the config's ``gst_style_input``; a JSON dict -> token
+    weights, its highest key checked against the number of tokens; anything else -> a wav path."""
+    gst = C.get("gst", None) or {}
+    if arg is None:
+        return gst.get("gst_style_input", None)
+    try:
+        style = json.loads(arg)
+    except ValueError:
+        return arg
+    if not isinstance(style, dict):
+        return arg
+    if max(map(int, style.keys())) >= gst["gst_style_tokens"]:
+        raise RuntimeError("The highest value of the gst_style dictionary key must be less than the number of GST "
+                           "Tokens, \n Highest dictionary key value: {} \n Number of GST tokens: {}".format(
+                               max(map(int, style.keys())), gst["gst_style_tokens"]))
+    return style
 
 
 def main(argv=None):
@@ -91,10 +112,8 @@ def main(argv=None):
     sid = None
     if not external and args.speaker_fileid is not None and args.speaker_fileid.isdigit():
         sid = int(args.speaker_fileid)
-    if args.gst_style is not None:
-        raise NotImplementedError("GST style input is outside the MI355X hot path (SURVEY.md §2)")
     wav = tts(model, vocoder_model, args.text, C, args.use_cuda, ap, use_griffin_lim, sid,
-              speaker_embedding=speaker_embedding)
+              speaker_embedding=speaker_embedding, gst_style=parse_gst_style(args.gst_style, C))
     file_name = args.text.replace(" ", "_")
     file_name = file_name.translate(str.maketrans("", "", string.punctuation.replace("_", ""))) + ".wav"
     out_path = os.path.join(args.out_path, file_name)

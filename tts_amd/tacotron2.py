@@ -72,8 +72,15 @@ class Tacotron2(TacotronHost):
                  gst_num_heads=4, gst_style_tokens=10, gst_use_speaker_embedding=False):
         super().__init__()
         unsupported = []
-        if gst:
-            unsupported.append("GST")
+        if gst and num_speakers <= 1:
+            unsupported.append("GST on a single-speaker model (gst=True needs num_speakers > 1)")
+        elif gst:
+            if gst_embedding_dim not in (128, 256, 512):
+                unsupported.append(f"gst_embedding_dim={gst_embedding_dim} (128, 256 or 512)")
+            if gst_num_heads not in (2, 4, 8):
+                unsupported.append(f"gst_num_heads={gst_num_heads} (2, 4 or 8)")
+            if not 1 <= int(gst_style_tokens) <= 32:
+                unsupported.append(f"gst_style_tokens={gst_style_tokens} (1 to 32)")
         if attn_type not in ("original", "graves"):
             unsupported.append(f"attn_type={attn_type}")
         if trans_agent and not forward_attn:
@@ -107,7 +114,14 @@ class Tacotron2(TacotronHost):
                                   windowing=bool(attn_win) and attn_type != "graves",
                                   forward_attn=bool(forward_attn) and attn_type != "graves",
                                   trans_agent=bool(trans_agent) and attn_type != "graves",
-                                  forward_attn_mask=bool(forward_attn and forward_attn_mask) and attn_type != "graves")
+                                  forward_attn_mask=bool(forward_attn and forward_attn_mask) and attn_type != "graves",
+                                  gst=bool(gst), gst_embedding_dim=int(gst_embedding_dim),
+                                  gst_num_heads=int(gst_num_heads), gst_style_tokens=int(gst_style_tokens),
+                                  gst_use_speaker_embedding=bool(gst_use_speaker_embedding))
+        self.gst = bool(gst)
+        self.gst_embedding_dim = int(gst_embedding_dim)
+        self.gst_style_tokens = int(gst_style_tokens)
+        self.gst_use_speaker_embedding = bool(gst_use_speaker_embedding)
         # models/tacotron2.py:50-58 / tacotron_abstract.py:76-81: a learned table unless the caller
         # gives per-sample embeddings of speaker_embedding_dim
         self.embeddings_per_sample = speaker_embedding_dim is not None
@@ -140,6 +154,98 @@ class Tacotron2(TacotronHost):
             raise IndexError("speaker id out of range")  # nn.Embedding raises too
         return ids.to(dev).contiguous(), None
 
+    def _style_check(self, style_mel, style_lengths, B):
+        """The style argument of one call, checked on the host (before anything asks for the device).
+        Returns None (no style: zeros), ("tokens", ids, weights) for a {token: weight} dict, or
+        ("mel", mel (Bs, N, 80), lengths) with Bs in (1, B). A mel of any shape is read as the
+        reference's ``inputs.view(B, 1, -1, 80)`` reads it (gst_layers.py:63): rows of 80 values of its
+        contiguous memory -- synthesis() hands over (1, 80, N), untransposed, and so may a caller."""
+        if not self.gst:
+            if style_mel is not None:
+                raise NotImplementedError("style_mel needs a model built with gst=True (GST style conditioning)")
+            if style_lengths is not None:
+                raise ValueError("style_lengths without style_mel")
+            return None
+        if style_mel is None:
+            if style_lengths is not None:
+                raise ValueError("style_lengths without style_mel")
+            return None
+        if isinstance(style_mel, dict):
+            if style_lengths is not None:
+                raise ValueError("style_lengths goes with a style mel, not with a token dict")
+            ids, ws = [], []
+            for k, v in style_mel.items():
+                k = int(k)
+                if not -self.gst_style_tokens <= k < self.gst_style_tokens:  # torch indexing: negatives wrap
+                    raise IndexError(f"index {k} is out of bounds for dimension 0 with size {self.gst_style_tokens}")
+                ids.append(k % self.gst_style_tokens)
+                ws.append(float(v))
+            if len(ids) > 64:
+                raise ValueError("at most 64 token weights")
+            return "tokens", ids, ws
+        mel = torch.as_tensor(style_mel)
+        if mel.dim() < 2 or mel.shape[0] < 1 or mel[0].numel() == 0 or mel[0].numel() % 80 != 0:
+            raise ValueError("style_mel must be a (B, N, 80) tensor (or any shape viewable as that) or a token dict")
+        mel = mel.contiguous().reshape(mel.shape[0], -1, 80)
+        Bs, N = mel.shape[:2]
+        if Bs not in (1, B):
+            raise ValueError("style_mel must have one row per utterance (or one row for all)")
+        lens = row_lengths(style_lengths, Bs, N, "style_lengths")
+        return "mel", mel, lens
+
+    def _style_vectors(self, eng, checked, B, spk_emb, dev):
+        """(B, gst_embedding_dim) style vectors on the device for ``_style_check``'s result, or None
+        (zeros). Caller holds ``eng.lock`` and has synced the weights."""
+        if checked is None:
+            return None
+        G = self.gst_embedding_dim
+        if checked[0] == "tokens":
+            one = torch.empty(G, device=dev, dtype=torch.float32)
+            eng.taco_style_tokens(checked[1], checked[2], one)
+            return one[None].expand(B, -1).contiguous()
+        _, mel, lens = checked
+        mel = mel.to(dev, torch.float32)
+        emb = spk_emb if self.cfg.gst_query_speaker_dim else None
+        if mel.shape[0] == 1 and B > 1 and emb is not None:  # one mel, but a query per speaker embedding
+            mel, lens = mel.expand(B, -1, -1), np.repeat(lens, B)
+        out = []
+        for b0 in range(0, mel.shape[0], SPEAKER_BATCH_LIMIT):
+            b1 = min(mel.shape[0], b0 + SPEAKER_BATCH_LIMIT)
+            N = int(lens[b0:b1].max())
+            st = torch.empty(b1 - b0, G, device=dev, dtype=torch.float32)
+            eng.taco_style_mel(mel[b0:b1, :N].contiguous(), lens[b0:b1],
+                               None if emb is None else emb[b0:b1].contiguous(), st)
+            out.append(st)
+        st = out[0] if len(out) == 1 else torch.cat(out)
+        return st.expand(B, -1).contiguous() if st.shape[0] != B else st
+
+    @torch.no_grad()
+    def style_embedding(self, style_mel, style_lengths=None, speaker_embeddings=None):
+        """The style vectors ``inference`` concatenates for ``style_mel`` (a mel tensor, a token dict
+        or None), (rows, gst_embedding_dim): ``gst_layer(style_mel, speaker_embeddings)`` of the
+        reference for a tensor. ``speaker_embeddings`` (rows, dim) is needed when the style
+        attention's query takes it (``gst_use_speaker_embedding`` with external embeddings)."""
+        if not self.gst:
+            raise NotImplementedError("style_embedding needs a model built with gst=True")
+        rows = 1 if style_mel is None or isinstance(style_mel, dict) else int(torch.as_tensor(style_mel).shape[0])
+        checked = self._style_check(style_mel, style_lengths, rows)
+        emb = None
+        if checked is not None and checked[0] == "mel" and self.cfg.gst_query_speaker_dim:
+            if speaker_embeddings is None:
+                raise ValueError("this model's style query takes the per-sample speaker_embeddings")
+            emb = torch.as_tensor(speaker_embeddings).reshape(-1, self.cfg.gst_query_speaker_dim)
+            if emb.shape[0] != rows:
+                raise ValueError("speaker_embeddings must have one row per style mel")
+        dev = self.device
+        eng = self._engine()  # a CPU model stops here: there is no CPU fallback
+        if checked is None:
+            return torch.zeros(1, self.gst_embedding_dim, device=dev)
+        if emb is not None:
+            emb = emb.to(dev, torch.float32).contiguous()
+        with eng.lock:
+            self._sync(eng)
+            return self._style_vectors(eng, checked, rows, emb, dev)
+
     def _load(self, eng):
         eng.load_tacotron(host_tensors(self, skip_prefixes=("coarse_decoder.", "decoder_backward.")), self.num_chars,
                           self.decoder.r_init, self.attn_norm, self.cfg.windowing, self.cfg.forward_attn,
@@ -157,15 +263,20 @@ class Tacotron2(TacotronHost):
 
     @torch.no_grad()
     def inference(self, text, speaker_ids=None, style_mel=None, speaker_embeddings=None,
-                  text_lengths: Optional[Sequence[int]] = None, max_decoder_steps=None):
-        if style_mel is not None:
-            raise NotImplementedError("GST style conditioning is not implemented (SURVEY.md §8f)")
+                  text_lengths: Optional[Sequence[int]] = None, max_decoder_steps=None, style_lengths=None):
+        """``style_mel`` (models built with ``gst=True``): a mel tensor (B or 1 rows of N frames;
+        with ``style_lengths`` row i uses its first N_i frames and equals the reference B = 1 call on
+        ``style_mel[i:i+1, :N_i]``), a ``{token: weight}`` dict (one style for all rows) or None (a
+        zero style vector), as tacotron_abstract.py:184-203."""
+        t = torch.as_tensor(text)
+        style = self._style_check(style_mel, style_lengths, 1 if t.dim() == 1 else t.shape[0])
         dev, eng, text, lens, ms, r, spk_ids, spk_emb, limit = self._prepare(
             text, speaker_ids, speaker_embeddings, text_lengths, max_decoder_steps)
         B = text.shape[0]
         outs = []
         with eng.lock:
             self._sync(eng)
+            style = self._style_vectors(eng, style, B, spk_emb, dev)
             for b0 in range(0, B, limit):
                 b1 = min(B, b0 + limit)
                 Tn = int(lens[b0:b1].max())
@@ -175,7 +286,8 @@ class Tacotron2(TacotronHost):
                 steps, status = eng.taco_infer(
                     sub, lens[b0:b1], r, ms[b0:b1], S_cap, self.decoder.stop_threshold, dec, post, align, stop,
                     speaker_ids=None if spk_ids is None else spk_ids[b0:b1].contiguous(),
-                    speaker_embeddings=None if spk_emb is None else spk_emb[b0:b1].contiguous())
+                    speaker_embeddings=None if spk_emb is None else spk_emb[b0:b1].contiguous(),
+                    **({} if style is None else {"style": style[b0:b1].contiguous()}))
                 outs.append((dec, post, align, stop, steps, status))
         self._last_call = (B, int(lens.max()), len(outs))
         return self._assemble(outs, text.shape, r, dev)
@@ -195,6 +307,9 @@ class Tacotron2(TacotronHost):
         ``mel_lengths=None``: every row has M frames. ``text_lengths`` need not be sorted. Models
         with ``double_decoder_consistency`` / ``bidirectional_decoder`` return the same 4-tuple (the
         reference adds two training-loss tensors). ``last_steps`` holds S_i, ``last_mel_lengths`` M_i.
+        A model with ``gst=True`` takes each row's style from its own teacher mel, as the reference
+        does (models/tacotron2.py:103-107): frames [0, M_i) followed by zeros up to S_i r, which is what
+        the B = 1 call on the zero-padded row sees.
         Training (``self.training``) stays out of scope."""
         if self.training:
             return super().forward()
@@ -235,6 +350,11 @@ class Tacotron2(TacotronHost):
         outs = []
         with eng.lock:
             self._sync(eng)
+            style = None
+            if self.gst:
+                frames = torch.arange(M, device=dev)[None, :, None] < torch.as_tensor(mlens, device=dev)[:, None, None]
+                smel = torch.where(frames, mel, torch.zeros((), device=dev))
+                style = self._style_vectors(eng, ("mel", smel, steps * r), B, spk_emb, dev)
             for b0 in range(0, B, SPEAKER_BATCH_LIMIT):
                 b1 = min(B, b0 + SPEAKER_BATCH_LIMIT)
                 Tn, Sn = int(lens[b0:b1].max()), int(steps[b0:b1].max())
@@ -242,7 +362,8 @@ class Tacotron2(TacotronHost):
                 eng.taco_forward(text[b0:b1, :Tn].contiguous(), lens[b0:b1], r, mel[b0:b1, :Sn * r].contiguous(),
                                  mlens[b0:b1], dec, post, align, stop,
                                  speaker_ids=None if spk_ids is None else spk_ids[b0:b1].contiguous(),
-                                 speaker_embeddings=None if spk_emb is None else spk_emb[b0:b1].contiguous())
+                                 speaker_embeddings=None if spk_emb is None else spk_emb[b0:b1].contiguous(),
+                                 **({} if style is None else {"style": style[b0:b1].contiguous()}))
                 outs.append((dec, post, align, stop))
         if len(outs) == 1 and outs[0][2].shape[1:] == (S, T):
             dec, post, align, stop = outs[0]
@@ -265,30 +386,40 @@ class Tacotron2(TacotronHost):
 
     @torch.no_grad()
     def inference_vocoded(self, text, vocoder, speaker_ids=None, speaker_embeddings=None,
-                          text_lengths: Optional[Sequence[int]] = None, max_decoder_steps=None):
+                          text_lengths: Optional[Sequence[int]] = None, max_decoder_steps=None, style_mel=None,
+                          style_lengths=None):
         """``inference`` followed by ``vocoder.inference(postnet_outputs.transpose(1, 2),
         lengths=last_mel_lengths)`` -- the pair TTS/server/synthesizer.py:150-159 runs -- in one
         library call when ``vocoder`` is a MultibandMelganGenerator on the same device and the batch
         fits one decode (tts_taco_mbmelgan_infer: the vocoder is launched on the decoded lengths the
         decode leaves on the device, no host round trip between the models); otherwise the two
         calls. Returns (decoder_outputs, postnet_outputs, alignments, stop_tokens, waveforms (B, 1,
-        hop * (M + 2 pad))), bit-identical to the two calls either way."""
+        hop * (M + 2 pad))), bit-identical to the two calls either way. With ``style_mel`` (GST models) it
+        is the two calls: the fused library entry takes no style vector."""
         return self._vocoded(text, vocoder, speaker_ids, speaker_embeddings, text_lengths, max_decoder_steps,
-                             submit=False).result()
+                             submit=False, style_mel=style_mel, style_lengths=style_lengths).result()
 
     @torch.no_grad()
     def inference_vocoded_submit(self, text, vocoder, speaker_ids=None, speaker_embeddings=None,
-                                 text_lengths: Optional[Sequence[int]] = None, max_decoder_steps=None):
+                                 text_lengths: Optional[Sequence[int]] = None, max_decoder_steps=None, style_mel=None,
+                                 style_lengths=None):
         """``inference_vocoded`` in two halves (tts_taco_mbmelgan_submit / _finish): returns a
         ``VocodedResult`` once the decode is done, with the vocoder still running on the device, so
         that the caller can queue the next batch behind it; ``.result()`` waits for the vocoder
         (re-running it in fp32 if its split-f16 operands left the f16 range) and returns what
         ``inference_vocoded`` returns. The decode outputs (``.outputs[:4]``) are ready at once."""
         return self._vocoded(text, vocoder, speaker_ids, speaker_embeddings, text_lengths, max_decoder_steps,
-                             submit=True)
+                             submit=True, style_mel=style_mel, style_lengths=style_lengths)
 
-    def _vocoded(self, text, vocoder, speaker_ids, speaker_embeddings, text_lengths, max_decoder_steps, submit):
+    def _vocoded(self, text, vocoder, speaker_ids, speaker_embeddings, text_lengths, max_decoder_steps, submit,
+                 style_mel=None, style_lengths=None):
         from .vocoder import MultibandMelganGenerator
+        if style_mel is not None or style_lengths is not None:
+            dec, post, align, stop = self.inference(text, speaker_ids=speaker_ids, style_mel=style_mel,
+                                                    speaker_embeddings=speaker_embeddings, text_lengths=text_lengths,
+                                                    max_decoder_steps=max_decoder_steps, style_lengths=style_lengths)
+            wav = vocoder.inference(post.transpose(1, 2), lengths=self.last_mel_lengths)
+            return VocodedResult((dec, post, align, stop), wav)
         dev, eng, text, lens, ms, r, spk_ids, spk_emb, limit = self._prepare(
             text, speaker_ids, speaker_embeddings, text_lengths, max_decoder_steps)
         B = text.shape[0]

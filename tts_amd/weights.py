@@ -73,6 +73,13 @@ def synth_tensor(name: str, shape: Tuple[int, ...], kind: str, seed: int,
     elif kind == "gru":  # nn.GRU / nn.GRUCell: U(-1/sqrt(H), 1/sqrt(H)), three gates
         H = shape[0] // 3
         x = u / math.sqrt(H)
+    elif kind == "gst_gru":  # the style encoder's nn.GRU, same default init
+        H = shape[0] // 3
+        x = u / math.sqrt(H)
+    elif kind == "gst_tokens":  # normal_(0, 0.5) (gst_layers.py:107): same std
+        x = u * (0.5 * math.sqrt(3.0))
+    elif kind == "gst_attn":  # nn.Linear default: U(-1/sqrt(fan_in), 1/sqrt(fan_in))
+        x = u / math.sqrt(shape[1])
     elif kind == "highway_gate_bias":  # Highway.T.bias is filled with -1 (layers/tacotron.py:87)
         x = -1.0 + 0.05 * u
     elif kind == "xavier":  # xavier_normal_ in the reference (speaker_encoder/model.py:49-54): same std
