@@ -44,6 +44,133 @@ def build_taco(cfg, sd, device="cuda"):
     return m.to(device).eval()
 
 
+# ---- taco_stops.npz: batches with stopnet-driven stops (tests/golden/make_stop_golden.py) ----
+STOP_MARGIN = 1e-2           # min |logit + bias| up to a row's stop (make_golden.py's margin)
+STOP_DRIFT_MAX = 1e-4 / 8    # the reference's own fp32-vs-fp64 postnet difference: MEL_TOL / 8
+STOP_SHRINK_BY = 8           # shrink-early order: the last batch tile's rows all stop by this step
+STOP_BATCHES = (17, 36, 64)  # the batches are rows 0..B-1 of a group, in the stored caller orders
+
+
+def decode_order(lens):
+    """The library's decode order for equal max_decoder_steps: stable sort by text length, descending
+    (api_taco.hip stage_decode_order); decode row i = caller row decode_order(lens)[i]."""
+    return np.argsort(-np.asarray(lens, np.int64), kind="stable")
+
+
+def stop_steps_from_logits(z, max_steps, steps=None):
+    """The reference's stop rule on biased logits z (n, max_steps): stop at the first t > 0 with z_t > 0
+    (sigmoid > 0.5), else at max_steps. Returns (steps, status 1 = stopnet / 2 = max steps, margin =
+    min |z_t| over the deciding steps 1..stop). `steps`: rows of z hold only that many logits."""
+    z = np.asarray(z, np.float64)
+    n = len(z)
+    out_steps, status, margin = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n)
+    for i in range(n):
+        zi = z[i, :max_steps if steps is None else int(steps[i])]
+        hit = np.nonzero(zi[1:] > 0)[0]
+        out_steps[i] = hit[0] + 2 if len(hit) else len(zi)
+        status[i] = 1 if len(hit) else 2
+        margin[i] = np.abs(zi[1:out_steps[i]]).min() if out_steps[i] > 1 else np.inf
+    return out_steps, status, margin
+
+
+def stop_spread_problems(lens, steps, status, max_steps, shrink_by=None):
+    """The spread conditions on one batch in caller order that are violated (none: an empty list).
+    Tiles are the decoder's 16-row batch tiles in decode order. With `shrink_by` the two conditions on
+    the last tile (it outlives a tile-0 stopper; it holds a max-steps row) are replaced: it must hold
+    only rows that stop by that step, while lower tiles hold both a row already frozen by then and a
+    live one."""
+    lens, steps, status = np.asarray(lens), np.asarray(steps), np.asarray(status)
+    B = len(lens)
+    o = decode_order(lens)
+    s, st = steps[o], status[o]
+    tiles = [slice(a, min(a + 16, B)) for a in range(0, B, 16)]
+    bad = []
+    if len(set(s.tolist())) < 6:
+        bad.append("fewer than 6 distinct step counts")
+    if 4 * int((st == 1).sum()) < B:
+        bad.append("fewer than a quarter of the rows stop by the stopnet")
+    if int((st == 2).sum()) < max(2, B // 10):
+        bad.append("too few rows run to max_decoder_steps")
+    if ((st == 2) & (s != max_steps)).any():
+        bad.append("a status-2 row below max_decoder_steps")
+    for k, t in enumerate(tiles):
+        if t.stop - t.start > 1 and not any(st[i] == 1 and (s[t] > s[i]).any() for i in range(t.start, t.stop)):
+            bad.append(f"tile {k}: no stopnet-stopped row beside a row that finishes later")
+    last = tiles[-1]
+    if shrink_by is None:
+        if len(tiles) > 1 and not ((st[tiles[0]] == 1) & (s[tiles[0]] < s[last].max())).any():
+            bad.append("no tile-0 row stops before the last tile finishes")
+        if not (st[last] == 2).any():
+            bad.append("the last tile holds no row that runs to max_decoder_steps")
+    else:
+        below = s[:last.start]
+        if not (s[last] <= shrink_by).all():
+            bad.append(f"a last-tile row runs past step {shrink_by}")
+        if not ((below <= s[last].max()).any() and (below > s[last].max()).any()):
+            bad.append("no frozen row beside a live one below the last tile when it falls away")
+    return bad
+
+
+def stop_tags(fx):
+    return [t for t in ("r2", "r1", "spk") if t + "_steps" in fx.files]
+
+
+def stop_fixture_problems(fx, tags=None):
+    """Every condition make_stop_golden.py asserts on its selection, re-derived from the stored data
+    alone (conditions on the reference, not on the code under test); the violated ones."""
+    bad = []
+    for tag in tags or stop_tags(fx):
+        p = tag + "_"
+        S = int(fx[p + "max_steps"])
+        lens, steps = fx[p + "lens"], fx[p + "steps"]
+        st, status, margin = stop_steps_from_logits(fx[p + "logits"], S, steps)
+        if not np.array_equal(st, steps):
+            bad.append(f"{tag}: the stored logits do not give the stored step counts")
+        if margin.min() < STOP_MARGIN:
+            bad.append(f"{tag}: stop margin {margin.min():.3e}")
+        if not np.array_equal(fx[p + "steps64"], steps):
+            bad.append(f"{tag}: the fp64 run stops elsewhere")
+        if fx[p + "drift64"].max() > STOP_DRIFT_MAX:
+            bad.append(f"{tag}: drift64 {fx[p + 'drift64'].max():.2e}")
+        if lens.min() < 1 or lens.max() > 30 or (len(lens) == 64 and ((lens == 1).sum() < 2 or len(set(lens.tolist())) < 12 or lens.max() < 25)):
+            bad.append(f"{tag}: text lengths not mixed over 1..30 with two rows of length 1")
+        orders = [f"order{n}" for n in STOP_BATCHES if n <= len(lens)] + (["order36_shrink"] if len(lens) >= 36 else [])
+        for name in orders:
+            o = fx[p + name]
+            n = int(name[5:7])
+            if sorted(o.tolist()) != list(range(n)):
+                bad.append(f"{tag} {name}: not an order of rows 0..{n - 1}")
+                continue
+            for msg in stop_spread_problems(lens[o], steps[o], status[o], S, STOP_SHRINK_BY if "shrink" in name else None):
+                bad.append(f"{tag} {name}: {msg}")
+    return bad
+
+
+def stop_model(fx, tag):
+    """(cfg, state dict) of a taco_stops group: the seeded model with its recorded gains and stop bias."""
+    cfg = TacotronConfig(**json.loads(str(fx[tag + "_cfg"])))
+    return taco_state_dict(None, seed=int(fx[tag + "_seed"]), overrides=json.loads(str(fx[tag + "_gains"])),
+                           stop_bias=float(fx[tag + "_stop_bias"]), cfg=cfg)
+
+
+def stop_batch(fx, r, rows, tag=None):
+    """Rows `rows` (caller order) of the taco_stops group `tag` (default f"r{r}") as one padded batch:
+    (ids (B, T_max) int64, text lengths, the reference's step counts, statuses, speaker ids or None).
+    Checks in numpy that these rows' stored stop logits keep the stop margin."""
+    tag = tag or f"r{r}"
+    p = tag + "_"
+    assert int(fx[p + "r"]) == r
+    rows = np.asarray(rows)
+    lens = fx[p + "lens"][rows]
+    steps, status, margin = stop_steps_from_logits(fx[p + "logits"][rows], int(fx[p + "max_steps"]), fx[p + "steps"][rows])
+    assert np.array_equal(steps, fx[p + "steps"][rows]) and margin.min() >= STOP_MARGIN, "stop_margin"
+    batch = np.zeros((len(rows), int(lens.max())), np.int64)
+    for k, i in enumerate(rows):
+        batch[k, :lens[k]] = fx[p + "ids"][i, :lens[k]]
+    spk = fx[p + "spk"][rows] if p + "spk" in fx.files else None
+    return batch, [int(x) for x in lens], steps, status, spk
+
+
 def melgan_state_dict(seed, cfg=None):
     cfg = cfg or MelganConfig()
     return cfg, synth_state_dict(melgan_spec(cfg, weight_norm=True), seed)

@@ -6,9 +6,11 @@ taken in order; the barrier's place must not change a single bit).
     python tools/taco_dump.py out.npz [n]     (n utterances, default 12; > 32 repeats the profile)
     python tools/taco_dump.py out.npz golden  (the taco_sigmoid fixture's three r = 2 utterances, built
                                                as tests/test_gpu_parity.py's batched test builds them)
+    python tools/taco_dump.py out.npz stops   (the taco_stops fixture's 17-row r = 2 batch in its stored
+                                               caller order: rows that stop by the stopnet, max steps 32)
 
 Every file also holds `path`, the decoder path of the call (Engine.decoder_stats(): 1 persistent,
-0 captured step graphs).
+0 captured step graphs), and `status` (per row, 1 = stopnet, 2 = max_decoder_steps).
 """
 import os
 import sys
@@ -50,11 +52,25 @@ def golden_run(dev, r=2):
     return m, m.inference(torch.from_numpy(batch).to(dev), text_lengths=[len(x) for x in ids])
 
 
+def stops_run(dev, r=2, B=17):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from helpers import build_taco, load_fixture, stop_batch, stop_model
+    fx = load_fixture("taco_stops")
+    cfg, sd = stop_model(fx, f"r{r}")
+    m = build_taco(cfg, sd, dev)
+    m.decoder.set_r(r)
+    m.decoder.max_decoder_steps = int(fx[f"r{r}_max_steps"])
+    m.decoder.verbose = False
+    batch, lens, _, _, _ = stop_batch(fx, r, fx[f"r{r}_order{B}"])
+    return m, m.inference(torch.from_numpy(batch).to(dev), text_lengths=lens)
+
+
 def main(path, mode="12"):
     dev = torch.device("cuda", 0)
-    taco, (dec, post, align, stop) = golden_run(dev) if mode == "golden" else bench_run(dev, int(mode))
+    taco, (dec, post, align, stop) = (golden_run(dev) if mode == "golden" else stops_run(dev) if mode == "stops"
+                                        else bench_run(dev, int(mode)))
     np.savez(path, dec=dec.cpu().numpy(), post=post.cpu().numpy(), align=align.cpu().numpy(),
-             stop=stop.cpu().numpy(), steps=np.asarray(taco.last_steps),
+             stop=stop.cpu().numpy(), steps=np.asarray(taco.last_steps), status=np.asarray(taco.last_status),
              path=np.asarray(get_engine("cuda:0").decoder_stats()[0]))
 
 
