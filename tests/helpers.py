@@ -53,7 +53,7 @@ STOP_BATCHES = (17, 36, 64)  # the batches are rows 0..B-1 of a group, in the st
 
 def decode_order(lens):
     """The library's decode order for equal max_decoder_steps: stable sort by text length, descending
-    (api_taco.hip stage_decode_order); decode row i = caller row decode_order(lens)[i]."""
+    (api_taco.hip stage_decode_order, a step of taco_run); decode row i = caller row decode_order(lens)[i]."""
     return np.argsort(-np.asarray(lens, np.int64), kind="stable")
 
 

@@ -8,6 +8,8 @@ taken in order; the barrier's place must not change a single bit).
                                                as tests/test_gpu_parity.py's batched test builds them)
     python tools/taco_dump.py out.npz stops   (the taco_stops fixture's 17-row r = 2 batch in its stored
                                                caller order: rows that stop by the stopnet, max steps 32)
+    python tools/taco_dump.py out.npz teacher (the taco_teacher fixture's four r = 2 rows as one batch
+                                               through the teacher-forced forward; no steps / status)
 
 Every file also holds `path`, the decoder path of the call (Engine.decoder_stats(): 1 persistent,
 0 captured step graphs), and `status` (per row, 1 = stopnet, 2 = max_decoder_steps).
@@ -65,8 +67,30 @@ def stops_run(dev, r=2, B=17):
     return m, m.inference(torch.from_numpy(batch).to(dev), text_lengths=lens)
 
 
+def teacher_run(dev, r=2):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from helpers import build_taco, load_fixture, taco_state_dict
+    fx = load_fixture("taco_teacher")
+    cfg, sd = taco_state_dict(fx, r=r)
+    m = build_taco(cfg, sd, dev)
+    m.decoder.set_r(r)
+    m.decoder.verbose = False
+    ids = [fx[f"r{r}_u{u}_ids"] for u in range(4)]
+    mels = [fx[f"r{r}_u{u}_mel"] for u in range(4)]
+    T, M = max(len(i) for i in ids), max(-(-len(x) // r) * r for x in mels)
+    text, mel = np.zeros((4, T), np.int64), np.full((4, M, 80), 1e3, np.float32)  # no row may read its padding
+    for b, (i, x) in enumerate(zip(ids, mels)):
+        text[b, :len(i)], mel[b, :len(x)] = i, x
+    return m.forward(torch.from_numpy(text).to(dev), torch.tensor([len(i) for i in ids]),
+                     torch.from_numpy(mel).to(dev), torch.tensor([len(x) for x in mels]))
+
+
 def main(path, mode="12"):
     dev = torch.device("cuda", 0)
+    if mode == "teacher":
+        dec, post, align, stop = teacher_run(dev)
+        return np.savez(path, dec=dec.cpu().numpy(), post=post.cpu().numpy(), align=align.cpu().numpy(),
+                        stop=stop.cpu().numpy(), path=np.asarray(get_engine("cuda:0").decoder_stats()[0]))
     taco, (dec, post, align, stop) = (golden_run(dev) if mode == "golden" else stops_run(dev) if mode == "stops"
                                         else bench_run(dev, int(mode)))
     np.savez(path, dec=dec.cpu().numpy(), post=post.cpu().numpy(), align=align.cpu().numpy(),

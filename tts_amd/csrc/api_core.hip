@@ -179,8 +179,8 @@ void run_conv(const ConvLayer& L, const ConvCall& c, hipStream_t st) {
   launch_conv(a, L.tile, st);
 }
 
-void enter(tts_ctx* c, void* stream) {
-  if (c->sv_live && !c->in_submit) {  // a fused submission's vocoder may still use the vocoder workspace
+void enter(tts_ctx* c, void* stream, bool join_voc) {
+  if (c->sv_live && join_voc) {  // a fused submission's vocoder may still use the vocoder workspace
     HIP_OK(hipStreamWaitEvent(c->s, c->ev_sv, 0));
     c->sv_live = false;
   }

@@ -6,18 +6,6 @@ using namespace ttsh;
 
 namespace {
 
-// the vocoder being enqueued uses a ticket slot's device lengths and range flag
-struct VocSlot {
-  tts_ctx* c;
-  VocSlot(tts_ctx* c_, unsigned* flag, int* lens) : c(c_) {
-    c->flag_override = flag;
-    c->vlens_override = lens;
-  }
-  ~VocSlot() {
-    c->flag_override = nullptr;
-    c->vlens_override = nullptr;
-  }
-};
 // the vocoder work just enqueued on sv: later entries join it (enter)
 void sv_mark(tts_ctx* c) {
   HIP_OK(hipEventRecord(c->ev_sv, c->sv));
@@ -39,16 +27,13 @@ void finish_ticket(tts_ctx* c, VocTicket& tk, void* stream) {
     HIP_OK(hipEventSynchronize(tk.ev));
     const int k = (int)(tk.id % NVT);
     if (c->pinned[TK_PIN + k]) {
-      c->x3_fallbacks++;
-      c->gemm_x3 = false;
-      try {  // on sv, behind any later submission's vocoder; the slot's lengths from the host
-        VocSlot vs(c, nullptr, vslot_lens(c, k));
-        mbmelgan_body(c, tk.d_post, tk.st, tk.lens.data(), tk.B, tk.M, tk.pad, tk.d_wav, false, c->sv);
-      } catch (...) {
-        c->gemm_x3 = true;
-        throw;
+      {  // on sv, behind any later submission's vocoder; the slot's lengths from the host
+        Fp32Rerun f32(c);
+        VocCall v{tk.d_post, tk.st, tk.lens.data(), tk.B, tk.M, tk.pad};
+        v.s = c->sv;
+        v.d_lens = vslot_lens(c, k);
+        mbmelgan_body(c, v, tk.d_wav);
       }
-      c->gemm_x3 = true;
       HIP_OK(hipEventRecord(tk.ev, c->sv));
       sv_mark(c);
     }
@@ -59,11 +44,13 @@ void finish_ticket(tts_ctx* c, VocTicket& tk, void* stream) {
 // Tacotron2 decode + MB-MelGAN, submitted: the vocoder is launched on the device-side decoded
 // lengths before the host waits for the decode's status words, and the call returns with the
 // vocoder still running (ticket); finish_ticket completes it.
-int64_t taco_mbmelgan_submit(tts_ctx* c, const int64_t* d_ids, const int32_t* h_lens, int B, int T_max, int r,
-                                    const int32_t* h_max_steps, int S_cap, float thr, const int64_t* d_spk_ids,
-                                    const float* d_spk_emb, float* d_dec, float* d_post, float* d_align,
-                                    float* d_stop, int pad, float* d_wav, int32_t* h_steps, int32_t* h_status,
-                                    void* stream) {
+int64_t taco_mbmelgan_submit(tts_ctx* c, TacoCall call, int pad, float* d_wav) {
+  const int64_t* d_ids = call.ids;
+  const int32_t *h_lens = call.h_lens, *h_max_steps = call.run.h_max_steps;
+  const int B = call.B, r = call.r, S_cap = call.run.S_cap;
+  float *d_dec = call.d_dec, *d_post = call.d_post, *d_align = call.d_align, *d_stop = call.d_stop;
+  int32_t *h_steps = call.run.h_steps, *h_status = call.run.h_status;
+  void* stream = call.stream;
   TTS_CHECK(d_ids && h_lens && h_max_steps && d_dec && d_post && d_align && d_stop && d_wav && h_steps && h_status,
             "null argument");
   TTS_CHECK(pad >= 0, "pad >= 0");
@@ -99,23 +86,15 @@ int64_t taco_mbmelgan_submit(tts_ctx* c, const int64_t* d_ids, const int32_t* h_
                 // samples apart until the decoded lengths are on the host
                 if (sv != c->s) HIP_OK(hipStreamWaitEvent(sv, c->ev_status, 0));
                 if (voc_x3) HIP_OK(hipMemsetAsync(vf, 0, 4, sv));
-                {
-                  VocSlot vs(c, vf, vl);
-                  mbmelgan_body(c, d_post, st, bound.data(), B, S_cap * r, pad, d_wav, /*dev_lens=*/true, sv);
-                }
+                VocCall v{d_post, st, bound.data(), B, S_cap * r, pad, /*dev_lens=*/true, sv, vl, vf};
+                mbmelgan_body(c, v, d_wav);
                 if (voc_x3) HIP_OK(hipMemcpyAsync(slot, vf, 4, hipMemcpyDeviceToHost, sv));
                 sv_mark(c);
               }};
   c->flag_read = false;
-  c->in_submit = true;  // this submission's Tacotron2 does not wait for earlier vocoders on sv
-  try {
-    taco_infer(c, d_ids, h_lens, B, T_max, r, h_max_steps, S_cap, thr, d_dec, d_post, d_align, d_stop, h_steps,
-               h_status, stream, d_spk_ids, d_spk_emb, &fv);
-  } catch (...) {
-    c->in_submit = false;
-    throw;
-  }
-  c->in_submit = false;
+  call.run.fv = &fv;  // this submission's Tacotron2 does not wait for earlier vocoders on sv
+  taco_run(c, call);
+  call.run.fv = nullptr;
   const bool taco_oflow = c->gemm_x3 && c->flag_read && c->pinned[PIN_FLAG];
   c->flag_read = false;
   int S = 0;
@@ -128,23 +107,17 @@ int64_t taco_mbmelgan_submit(tts_ctx* c, const int64_t* d_ids, const int32_t* h_
   if (taco_oflow) {
     // the decode left the f16 range: decode and vocoder again on the fp32 kernels (the split
     // vocoder already queued is overwritten), as the two separate calls would each have done
-    c->x3_fallbacks++;
-    c->gemm_x3 = false;
-    sv_join(c);  // the split vocoder queued on sv writes d_wav before the fp32 one below
-    try {
-      taco_infer(c, d_ids, h_lens, B, T_max, r, h_max_steps, S_cap, thr, d_dec, d_post, d_align, d_stop, h_steps,
-                 h_status, stream, d_spk_ids, d_spk_emb);
+    {
+      Fp32Rerun f32(c);
+      sv_join(c);  // the split vocoder queued on sv writes d_wav before the fp32 one below
+      taco_run(c, call);
       S = 0;
       for (int b = 0; b < B; ++b) {
         S = std::max(S, (int)h_steps[b]);
         mlens[b] = h_steps[b] * r;
       }
-      mbmelgan_body(c, d_post, st, mlens.data(), B, S * r, pad, d_wav);
-    } catch (...) {
-      c->gemm_x3 = true;
-      throw;
+      mbmelgan_body(c, VocCall{d_post, st, mlens.data(), B, S * r, pad}, d_wav);
     }
-    c->gemm_x3 = true;
     leave(c, stream);
     return id;
   }
@@ -177,11 +150,15 @@ int tts_taco_mbmelgan_submit(tts_ctx* c, const int64_t* d_ids, const int32_t* h_
                              const float* d_spk_emb, float* d_dec, float* d_post, float* d_align, float* d_stop,
                              int pad, float* d_wav, int32_t* h_steps, int32_t* h_status, int64_t* h_ticket,
                              void* stream) {
+  TacoCall call;
+  call.ids = d_ids, call.h_lens = h_lens, call.B = B, call.T_max = T_max, call.r = r, call.stream = stream;
+  call.d_spk_ids = d_spk_ids, call.d_spk_emb = d_spk_emb;
+  call.d_dec = d_dec, call.d_post = d_post, call.d_align = d_align, call.d_stop = d_stop;
+  call.run = TacoFree{h_max_steps, S_cap, thr, h_steps, h_status};
   return guarded_ctx(c, [&] {
     TTS_CHECK(c && h_ticket, "null argument");
     DeviceGuard g(c->device);
-    *h_ticket = taco_mbmelgan_submit(c, d_ids, h_lens, B, T_max, r, h_max_steps, S_cap, thr, d_spk_ids, d_spk_emb,
-                                     d_dec, d_post, d_align, d_stop, pad, d_wav, h_steps, h_status, stream);
+    *h_ticket = taco_mbmelgan_submit(c, call, pad, d_wav);
   });
 }
 
@@ -198,11 +175,14 @@ int tts_taco_mbmelgan_infer(tts_ctx* c, const int64_t* d_ids, const int32_t* h_l
                             const int32_t* h_max_steps, int S_cap, float thr, const int64_t* d_spk_ids,
                             const float* d_spk_emb, float* d_dec, float* d_post, float* d_align, float* d_stop,
                             int pad, float* d_wav, int32_t* h_steps, int32_t* h_status, void* stream) {
+  TacoCall call;
+  call.ids = d_ids, call.h_lens = h_lens, call.B = B, call.T_max = T_max, call.r = r, call.stream = stream;
+  call.d_spk_ids = d_spk_ids, call.d_spk_emb = d_spk_emb;
+  call.d_dec = d_dec, call.d_post = d_post, call.d_align = d_align, call.d_stop = d_stop;
+  call.run = TacoFree{h_max_steps, S_cap, thr, h_steps, h_status};
   return guarded_ctx(c, [&] {
     DeviceGuard g(c->device);
-    const int64_t id = taco_mbmelgan_submit(c, d_ids, h_lens, B, T_max, r, h_max_steps, S_cap, thr, d_spk_ids,
-                                            d_spk_emb, d_dec, d_post, d_align, d_stop, pad, d_wav, h_steps, h_status,
-                                            stream);
+    const int64_t id = taco_mbmelgan_submit(c, call, pad, d_wav);
     VocTicket& tk = c->vt[id % NVT];
     if (tk.id == id) finish_ticket(c, tk, stream);
     HIP_OK(hipStreamSynchronize(c->sv));  // returns with the call's work done, as before

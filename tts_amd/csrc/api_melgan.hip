@@ -135,10 +135,15 @@ static void melgan_finalize(tts_ctx* c, int in_ch, int out_ch, int base, const i
   G.ready = true;
 }
 
-int ttsh::run_generator(tts_ctx* c, const float* mel, const int32_t* h_lens, int B, int M_max, int pad, float* out,
-                  hipStream_t s, GenTail* tail, const int64_t* mel_strides, bool dev_lens) {
+int ttsh::run_generator(tts_ctx* c, const VocCall& v, float* out, GenTail* tail) {
   auto& G = c->mg;
   auto& W = c->mws;
+  const float* mel = v.mel;
+  const int64_t* mel_strides = v.mel_strides;
+  const int32_t* h_lens = v.h_lens;
+  const int B = v.B, M_max = v.M_max, pad = v.pad;
+  const bool dev_lens = v.dev_lens;
+  hipStream_t s = v.s ? v.s : c->s;
   TTS_CHECK(G.ready, "melgan weights not finalized");
   TTS_CHECK(B >= 1, "B >= 1");
   for (int b = 0; b < B && !dev_lens; ++b) {
@@ -161,7 +166,7 @@ int ttsh::run_generator(tts_ctx* c, const float* mel, const int32_t* h_lens, int
     }
   }
   // device lengths: the ticket slot's (a fused submission's vocoder) or the workspace's
-  int* vld = c->vlens_override;
+  int* vld = v.d_lens;
   if (!vld) {
     W.lens.ensure(B * 4);
     vld = W.lens.i();
@@ -170,11 +175,11 @@ int ttsh::run_generator(tts_ctx* c, const float* mel, const int32_t* h_lens, int
   W.xb.ensure((size_t)B * maxelems * 4);
   std::vector<int> lens(h_lens, h_lens + B);
   if (!dev_lens) HIP_OK(hipMemcpyAsync(vld, lens.data(), B * 4, hipMemcpyHostToDevice, s));
-  else TTS_CHECK(c->vlens_override || W.lens.bytes >= (size_t)B * 4, "vocoder lengths buffer");
+  else TTS_CHECK(v.d_lens || W.lens.bytes >= (size_t)B * 4, "vocoder lengths buffer");
   ConvCall cc;
   cc.lens = vld;
   cc.B = B;
-  cc.oflow = x3_flag(c);
+  cc.oflow = c->gemm_x3 && v.flag ? v.flag : x3_flag(c);
   cc.len_add = 2 * pad;
   // layers[0..1]: replicate pad (inference_padding) + ReflectionPad1d(3) + Conv1d(k7)
   if (mel_strides) {
@@ -340,27 +345,27 @@ int ttsh::run_generator(tts_ctx* c, const float* mel, const int32_t* h_lens, int
   return up;
 }
 
-void ttsh::mbmelgan_body(tts_ctx* c, const float* d_mel, const int64_t* mel_strides, const int32_t* h_lens, int B,
-                         int M_max, int pad, float* d_wav, bool dev_lens, hipStream_t s) {
-  if (!s) s = c->s;
+void ttsh::mbmelgan_body(tts_ctx* c, const VocCall& v, float* d_wav) {
+  hipStream_t s = v.s ? v.s : c->s;
+  const int B = v.B, pad = v.pad;
   auto& G = c->mg;
   int up = 1;
   for (int u : G.ups) up *= u;
-  const long Ls = (long)(M_max + 2 * pad) * up;
+  const long Ls = (long)(v.M_max + 2 * pad) * up;
   const bool fused = G.out_ch == 4 && G.taps == 62 && (G.C_last == 32 || G.C_last == 48);
   if (fused) {  // launch_out_pqmf writes the rows' zero padding itself
     GenTail t;
-    run_generator(c, d_mel, h_lens, B, M_max, pad, nullptr, s, &t, mel_strides, dev_lens);
+    run_generator(c, v, nullptr, &t);
     TTS_CHECK(t.Ls == Ls, "generator length bookkeeping");
-    const int* dl = c->vlens_override ? c->vlens_override : c->mws.lens.i();
+    const int* dl = v.d_lens ? v.d_lens : c->mws.lens.i();
     TTS_CHECK(launch_out_pqmf(t.x, (long)t.C * t.Ls, t.Ls, t.C, G.out_w.f(), G.out_b.f(), G.G.f(), G.out_ch,
                               G.taps, dl, 2 * pad, up, (int)Ls, B, d_wav, (long)G.out_ch * Ls, s),
               "fused output/PQMF shape not covered");
   } else {
     HIP_OK(hipMemsetAsync(d_wav, 0, (size_t)B * G.out_ch * Ls * 4, s));
     c->mws.bands.ensure((size_t)B * G.out_ch * Ls * 4);
-    run_generator(c, d_mel, h_lens, B, M_max, pad, c->mws.bands.f(), s, nullptr, mel_strides, dev_lens);
-    const int* dl = c->vlens_override ? c->vlens_override : c->mws.lens.i();
+    run_generator(c, v, c->mws.bands.f());
+    const int* dl = v.d_lens ? v.d_lens : c->mws.lens.i();
     launch_pqmf_synthesis(c->mws.bands.f(), (long)G.out_ch * Ls, Ls, G.G.f(), G.out_ch, G.taps, dl,
                           2 * pad, up, (int)Ls, B, d_wav, (long)G.out_ch * Ls, s);
   }
@@ -382,7 +387,7 @@ static int melgan_infer_impl(tts_ctx* c, const float* d_mel, const int64_t* mel_
         TTS_CHECK(pad >= 0, "pad >= 0");
         TTS_CHECK(c->mg.ready && c->mg.pqmf, "melgan (with PQMF) not finalized");
       },
-      [&] { mbmelgan_body(c, d_mel, mel_strides, h_lens, B, M_max, pad, d_wav); });
+      [&] { mbmelgan_body(c, VocCall{d_mel, mel_strides, h_lens, B, M_max, pad}, d_wav); });
 }
 
 extern "C" {
@@ -411,7 +416,7 @@ int tts_melgan_generator(tts_ctx* c, const float* d_mel, const int32_t* h_lens, 
         TTS_CHECK(c && d_mel && h_lens && d_out, "null argument");
         TTS_CHECK(pad >= 0, "pad >= 0");
       },
-      [&] { run_generator(c, d_mel, h_lens, B, M_max, pad, d_out, c->s); });
+      [&] { run_generator(c, VocCall{d_mel, nullptr, h_lens, B, M_max, pad}, d_out); });
 }
 
 int tts_melgan_infer(tts_ctx* c, const float* d_mel, const int32_t* h_lens, int B, int M_max, int pad,

@@ -1,23 +1,18 @@
-// Tacotron2, running: the decoder step launches and their captured graphs, the encoder and
-// postnet, the persistent decoder, taco_infer, the teacher-forced taco_forward, and the tts_taco_*
-// inference entry points.
+// Tacotron2, running: the encoder and postnet, the persistent decoder, taco_run (one driver for the
+// free-running and the teacher-forced decode), and the tts_taco_* inference entry points.
 #include "host.h"
 #include "decoder.h"
 #include "gsync.h"
 #include "split16.h"
 #include "switches.h"
 
-#include <cmath>
 #include <cstdio>
-#include <cstring>
 
 using namespace ttsh;
 
-namespace {
+DecCtlBlock* ttsh::ctl_block(const TacoWS& W) { return static_cast<DecCtlBlock*>(W.ctl.p); }
 
-DecCtlBlock* ctl_block(const TacoWS& W) { return static_cast<DecCtlBlock*>(W.ctl.p); }
-
-DecDev make_dev(tts_ctx* c, int Bact) {
+DecDev ttsh::make_dev(tts_ctx* c, int Bact) {
   auto& W = c->tws;
   DecDev d{};
   DecCtlBlock* cb = ctl_block(W);
@@ -36,142 +31,7 @@ DecDev make_dev(tts_ctx* c, int Bact) {
   return d;
 }
 
-// columns [k0, k0 + K) of a fragment-order activation with Ktot columns
-SkSeg seg(const float* base, int Ktot, int k0, int K) {
-  SkSeg s;
-  s.ptr = base + (long)(k0 / 16) * 256;
-  s.ms = 16 * Ktot;
-  s.K = K;
-  return s;
-}
-
-// the 5 launches of decoder step j of a chunk (parity j & 1 selects the h_dec buffer) over the
-// first MT batch tiles (rows >= 16*MT must all be finished)
-void enqueue_step(tts_ctx* c, int j, int which_only, hipStream_t s, int MT) {
-  auto& M = c->taco;
-  auto& W = c->tws;
-  const DecDev d = make_dev(c, std::min(W.B, 16 * MT));
-  const int r = W.r, YLD = 80 * M.r_init;
-  float* hd_cur = (j & 1) ? W.hdec1.f() : W.hdec0.f();
-  float* hd_nxt = (j & 1) ? W.hdec0.f() : W.hdec1.f();
-  if (which_only < 0 || which_only == 1) {  // K1: prenet layers 1+2 || stop(t-1)
-    SkArgs a{};
-    a.njobs = 2;
-    a.MT = MT;
-    SkJob& J = a.job[0];  // layer 1 (result kept in LDS)
-    J.seg[0] = seg(W.y.f(), YLD, 80 * (r - 1), 80);
-    J.nseg = 1;
-    J.K = 80;
-    J.W = M.pre1.f();
-    J.ntiles = 16;
-    SkJob& J2 = a.job[1];  // layer 2
-    J2.K = 256;
-    J2.W = M.pre2.f();
-    J2.ntiles = 16;
-    J2.out = W.pb.f();
-    J2.out_ld = 256;
-    J2.out_frag = 1;
-    StopArgs st{};
-    st.part = W.spart.f();
-    st.threshold = W.thr;
-    launch_prenet_stop(a, d, st, j, s);
-  }
-  if (which_only < 0 || which_only == 3) {  // K2: attention_rnn + partial query projection
-    SkArgs a{};
-    a.njobs = 1;
-    a.MT = MT;
-    SkJob& J = a.job[0];
-    J.seg[0] = seg(W.pb.f(), 256, 0, 256);
-    J.nseg = 1;
-    J.K = 256;
-    J.W = M.att_p.f();
-    J.ntiles = 256;
-    J.epi = EPI_LSTM;
-    J.addin = W.gatt.f();
-    J.addin_ld = 4096;
-    J.h_out = W.hatt.f();
-    J.c_state = W.catt.f();
-    J.hc_ld = 1024;
-    J.WqT = M.WqT.f();
-    J.pq_part = W.pq.f();
-    J.pq_cap = 128;
-    launch_skinny(a, d, j, 2, 4, s);  // 128 workgroups of 8 units: 128 query partials
-  }
-  if (which_only < 0 || which_only == 4) {  // K3: attention
-    AttnArgs p{};
-    p.pq_part = W.pq.f();
-    p.npq = 128;
-    p.Bp = MT * 16;
-    p.alpha = W.alpha.f();
-    p.alpha_cum = W.acum.f();
-    p.Wloc = M.Wloc.f();
-    p.WdT = M.Wdense.f();
-    p.v = M.v.f();
-    p.bv = M.bv;
-    p.penc = W.penc.f();
-    p.energy = W.energy.f();
-    p.enc = W.enc.f();
-    p.ctx = W.ctx.f();
-    p.part_s = W.aps.f();
-    p.part_m = W.apm.f();
-    p.part_u = W.apu.f();
-    p.counter = reinterpret_cast<unsigned*>(W.acnt.p);
-    p.nchmax = (W.T_max + 15) / 16;
-    p.softmax = M.softmax;
-    launch_attention(p, d, j, s);
-  }
-  if (which_only < 0 || which_only == 0) {  // K4: decoder_rnn LSTMCell
-    SkArgs a{};
-    a.njobs = 1;
-    a.MT = MT;
-    SkJob& J = a.job[0];
-    J.seg[0] = seg(W.hatt.f(), 1024, 0, 1024);
-    J.seg[1] = seg(W.ctx.f(), 512, 0, 512);
-    J.seg[2] = seg(hd_cur, 1024, 0, 1024);
-    J.nseg = 3;
-    J.K = 2560;
-    J.W = M.dec_w.f();
-    J.ntiles = 256;
-    J.epi = EPI_LSTM;
-    J.bias = M.dec_bias.f();
-    J.h_out = hd_nxt;
-    J.c_state = W.cdec.f();
-    J.hc_ld = 1024;
-    launch_skinny(a, d, j, 1, 4, s);
-  }
-  if (which_only < 0 || which_only == 5) {  // K5: projection + stop logit || next attention_rnn ctx/h part
-    SkArgs a{};
-    a.njobs = 2;
-    a.MT = MT;
-    SkJob& J = a.job[0];
-    J.seg[0] = seg(hd_nxt, 1024, 0, 1024);
-    J.seg[1] = seg(W.ctx.f(), 512, 0, 512);
-    J.nseg = 2;
-    J.K = 1536;
-    J.W = M.proj_w.f();
-    J.ntiles = 1 + 5 * r;  // stopnet tile + the first r frames (tacotron2.py:297)
-    J.epi = EPI_STORE;
-    J.bias = M.proj_b.f();
-    J.out = W.y.f();
-    J.out_ld = YLD;
-    J.out_frag = 1;
-    J.frames_r = r;
-    J.lead_stop = 1;
-    J.stop_part = W.spart.f();
-    SkJob& J2 = a.job[1];  // (+ biases)
-    J2.seg[0] = seg(W.ctx.f(), 512, 0, 512);
-    J2.seg[1] = seg(W.hatt.f(), 1024, 0, 1024);
-    J2.nseg = 2;
-    J2.K = 1536;
-    J2.W = M.att_pre.f();
-    J2.ntiles = 256;
-    J2.epi = EPI_STORE;
-    J2.bias = M.att_bias.f();
-    J2.out = W.gatt.f();
-    J2.out_ld = 4096;
-    launch_skinny(a, d, j, 1, 4, s);
-  }
-}
+namespace {
 
 __global__ void bcast_rows_kernel(const float* src, int n, float* dst, int rows) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n * rows; i += gridDim.x * blockDim.x)
@@ -467,25 +327,6 @@ __global__ void taco_status_kernel(const unsigned* enc_bar, int nenc, const unsi
   if (i == 0) st[TS_FLAG] = flag ? (int)*flag : 0;
 }
 
-// CHUNK-step graph for batch tile count MT (captured once per configuration)
-hipGraphExec_t step_graph(tts_ctx* c, int MT, hipStream_t s) {
-  auto& W = c->tws;
-  if (W.graphs[MT]) return W.graphs[MT];
-  hipGraph_t g;
-  HIP_OK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-  try {
-    for (int j = 0; j < CHUNK; ++j) enqueue_step(c, j, -1, s, MT);
-    launch_dec_advance(&ctl_block(W)->ctl, CHUNK, s);
-  } catch (...) {
-    hipGraph_t tmp;
-    (void)hipStreamEndCapture(s, &tmp);
-    throw;
-  }
-  HIP_OK(hipStreamEndCapture(s, &g));
-  HIP_OK(hipGraphInstantiate(&W.graphs[MT], g, nullptr, nullptr, 0));
-  HIP_OK(hipGraphDestroy(g));
-  return W.graphs[MT];
-}
 
 bool use_persistent(tts_ctx* c) {
   if (sw::decoder_graph()) return false;
@@ -656,7 +497,7 @@ void launch_cascade(tts_ctx* c, PArgs a, hipStream_t s) {
   c->dec_nlaunch = 0;
   c->dec_presplit = persist_presplit(a);
   for (int mt = W.MT; mt >= 1; --mt) {
-    const int li = W.MT - mt;  // launch index: its barrier block (armed in taco_infer's state fill)
+    const int li = W.MT - mt;  // launch index: its barrier block (armed in taco_run's state fill)
     const bool traced = trace_p && li == trace_li;  // one launch is traced
     a.bar = reinterpret_cast<unsigned*>(W.pbar.p) + BAR_WORDS * W.pslot[li];
     a.base_out = W.stat.i() + TS_END + li;
@@ -674,7 +515,7 @@ void launch_cascade(tts_ctx* c, PArgs a, hipStream_t s) {
 }
 
 // the whole decode on the persistent kernel (decoder_persist.hip)
-// teach_steps > 0: teacher mode on W.teach (taco_forward)
+// teach_steps > 0: teacher mode on W.teach (a teacher-forced call)
 void run_persistent(tts_ctx* c, int r, float thr, hipStream_t s, int teach_steps = 0) {
   build_pj(c, r);
   grow<float>(c->tws.spkb, (size_t)64 * (8320 + 112 * 16), c->tws.gen);
@@ -689,7 +530,7 @@ void run_persistent(tts_ctx* c, int r, float thr, hipStream_t s, int teach_steps
   launch_cascade(c, a, s);
 }
 
-// ---- the steps of taco_infer, in call order ----
+// ---- the steps of taco_run, in call order ----
 
 // returns the largest max_decoder_steps of the batch
 int check_infer_args(const TacoModel& M, const int32_t* h_lens, int B, int T_max, int r, const int32_t* h_max_steps,
@@ -813,47 +654,11 @@ void fill_decoder_state(tts_ctx* c, int B, int T_max, int S_cap, int r, bool per
   HIP_OK(hipGetLastError());
 }
 
-// the decode as captured CHUNK-step graphs (decoder.hip's per-step kernels), polled by the host
-void run_graph_decoder(tts_ctx* c, int B, int T_max, int S_cap, int r, float thr, int max_ms, hipStream_t s) {
-  auto& W = c->tws;
-  // step graphs, cached per configuration / buffer generation
-  if (W.graph_gen != W.gen || W.gB != B || W.gT != T_max || W.gS != S_cap || W.gr != r || W.gthr != thr) {
-    for (auto& ge : W.graphs)
-      if (ge) {
-        HIP_OK(hipGraphExecDestroy(ge));
-        ge = nullptr;
-      }
-    W.graph_gen = W.gen;
-    W.gB = B;
-    W.gT = T_max;
-    W.gS = S_cap;
-    W.gr = r;
-    W.gthr = thr;
-  }
-  for (int mt = 1; mt <= W.MT; ++mt) step_graph(c, mt, s);
-  // run chunks until every utterance is done (checked one chunk behind) or t > max steps; drop
-  // to fewer batch tiles once the trailing rows have all finished
-  const int chunks_max = max_ms / CHUNK + 1;  // covers t = max_ms (stop of the last step)
-  bool done = false;
-  int mt = W.MT;
-  for (int ch = 0; ch < chunks_max && !done; ++ch) {
-    HIP_OK(hipGraphLaunch(W.graphs[mt], s));
-    // {all_done, active_tiles} into the polling pair of this chunk's parity
-    HIP_OK(hipMemcpyAsync(&c->pinned[PIN_CHUNK + 2 * (ch & 1)], &ctl_block(W)->ctl.all_done, 8, hipMemcpyDeviceToHost, s));
-    HIP_OK(hipEventRecord(c->ev_chunk[ch & 1], s));
-    if (ch >= 1) {
-      HIP_OK(hipEventSynchronize(c->ev_chunk[(ch - 1) & 1]));
-      const int* pv = &c->pinned[PIN_CHUNK + 2 * ((ch - 1) & 1)];
-      if (pv[0]) done = true;
-      else if (pv[1] >= 1 && pv[1] < mt) mt = pv[1];
-    }
-  }
-}
 
 // postnet over each row's own frames: lengths from the decoder results on the device, grid sized
 // by S_cap (tiles past a row's length exit at entry), so the decode needs no host round trip; then
 // the scatter back to the caller's row order: output row b <- decode row inv[b]
-// ml (taco_forward): the rows' mel lengths M_i in decode order; the decoder outputs are zeroed at
+// ml (a teacher-forced call): the rows' mel lengths M_i in decode order; the decoder outputs are zeroed at
 // frames >= M_i before the postnet, its output after it (the reference's output mask,
 // models/tacotron2.py:123-130)
 void run_postnet_scatter(tts_ctx* c, int B, int T_max, int S_cap, int r, float* d_dec, float* d_post, float* d_align,
@@ -917,103 +722,83 @@ void report_rows(tts_ctx* c, const std::vector<int>& perm, int32_t* h_steps, int
 
 }  // namespace
 
-void ttsh::taco_infer(tts_ctx* c, const int64_t* ids, const int32_t* h_lens, int B, int T_max, int r,
-                const int32_t* h_max_steps, int S_cap, float thr, float* d_dec, float* d_post, float* d_align,
-                float* d_stop, int32_t* h_steps, int32_t* h_status, void* stream,
-                const int64_t* d_spk_ids, const float* d_spk_emb, const FusedVoc* fv, const float* d_style) {
-  const int max_ms = check_infer_args(c->taco, h_lens, B, T_max, r, h_max_steps, S_cap);
+// One Tacotron2 call, free-running or teacher-forced (k.teach set: Tacotron2.forward in eval). The
+// teacher-forced decode is the same sequence with the prenet fed from the ground-truth mel
+// (teacher_prenet.hip + the persistent decoder's teacher variant), exactly S_i = ceil(M_i / r) steps
+// per row, raw stop logits, and the reference's output mask.
+void ttsh::taco_run(tts_ctx* c, const TacoCall& k) {
+  auto& M = c->taco;
+  const TacoTeach* t = k.teach;
+  const int B = k.B, T_max = k.T_max, r = k.r;
+  const FusedVoc* fv = t ? nullptr : k.run.fv;
+  const int32_t* h_max_steps = k.run.h_max_steps;
+  int S_cap = k.run.S_cap;
+  int32_t tsteps[BMAX], rsteps[BMAX], rstatus[BMAX];
+  if (t) {  // the step counts come from the mel lengths
+    TTS_CHECK(M.ready, "tacotron2 weights not finalized");
+    TTS_CHECK(t->M_max >= 1 && t->M_max <= (1 << 20) && r >= 1 && t->M_max % r == 0,
+              "M_max must be a positive multiple of r");
+    TTS_CHECK(!M.windowing && !M.forward_attn && !M.graves,
+              "teacher-forced forward: attention windowing, forward attention and Graves attention are not implemented");
+    TTS_CHECK(B >= 1 && B <= BMAX, "B must be in [1, 64]");
+    for (int b = 0; b < B; ++b) {
+      TTS_CHECK(t->h_mel_lens[b] >= 1 && t->h_mel_lens[b] <= t->M_max, "mel lens out of range");
+      tsteps[b] = (t->h_mel_lens[b] + r - 1) / r;
+    }
+    h_max_steps = tsteps;
+    S_cap = t->M_max / r;
+  }
+  const int max_ms = check_infer_args(M, k.h_lens, B, T_max, r, h_max_steps, S_cap);
   taco_workspace(c, B, T_max, S_cap, r);
   auto& W = c->tws;
+  if (t) grow<float>(W.teach, (size_t)S_cap * W.MT * 16 * 256, W.gen);
   hipStream_t s = c->s;
-  enter(c, stream);
+  enter(c, k.stream, /*join_voc=*/!fv);  // a fused submission's decode does not wait for earlier vocoders
   // a fused call's range flag is zeroed by the setup launch (no separate fill)
-  const std::vector<int> perm = stage_decode_order(c, h_lens, h_max_steps, B, fv ? x3_flag(c) : nullptr, s);
-  W.thr = thr;
+  const std::vector<int> perm = stage_decode_order(c, k.h_lens, h_max_steps, B, fv ? x3_flag(c) : nullptr, s);
+  W.thr = t ? 0.5f : k.run.thr;  // teacher-forced: unused, a row never stops by its stop token
   const bool persist = use_persistent(c);
-  TTS_CHECK(!c->taco.variant() || persist, "BN prenet / attention windowing / forward / Graves attention run on "
-                                           "the persistent decoder only (<= 64 utterances per call on a 256-CU "
-                                           "device)");
-  stage_speakers(c, d_spk_ids, d_spk_emb, d_style, B, s);
-  run_encoder_penc(c, ids, B, T_max, s);
+  TTS_CHECK(!t || persist, "teacher-forced forward runs on the persistent decoder only (<= 64 utterances per "
+                           "call on a 256-CU device, TTS_DECODER=graph unset)");
+  TTS_CHECK(!M.variant() || persist, "BN prenet / attention windowing / forward / Graves attention run on "
+                                     "the persistent decoder only (<= 64 utterances per call on a 256-CU "
+                                     "device)");
+  stage_speakers(c, k.d_spk_ids, k.d_spk_emb, k.d_style, B, s);
+  run_encoder_penc(c, k.ids, B, T_max, s);
   if (persist && !W.pslot_cal) {  // ordered after the caller's work (enter above) and this call's encoder
     pick_barrier_blocks(reinterpret_cast<unsigned*>(W.pbar.p), PBAR_CAND, PMAX_LAUNCH, W.pslot, s);
     W.pslot_cal = true;
   }
   fill_decoder_state(c, B, T_max, S_cap, r, persist, s);
+  MelLens ml{};  // teacher-forced: the output mask's lengths, decode order
+  if (t) {  // prenet layer 1 of every ground-truth frame the decoder will be fed, into W.teach
+    TeachArgs ta{};
+    ta.mel = t->d_mel;
+    ta.mel_b = (long)t->M_max * 80;
+    ta.map = W.map.i();
+    ta.max_steps = ctl_block(W)->max_steps;
+    ta.W1 = M.pre1.f();
+    ta.b1 = M.prenet_bn ? M.pre1_b0.f() : nullptr;
+    ta.teach = W.teach.f();
+    ta.B = B;
+    ta.Bp = W.MT * 16;
+    ta.r = r;
+    ta.steps = S_cap;
+    launch_teacher_prenet(ta, s);
+    for (int i = 0; i < B; ++i) ml.M[i] = t->h_mel_lens[perm[i]];
+  }
   c->dec_path = persist ? 1 : 0;
-  if (persist) run_persistent(c, r, thr, s);
-  else run_graph_decoder(c, B, T_max, S_cap, r, thr, max_ms, s);
-  run_postnet_scatter(c, B, T_max, S_cap, r, d_dec, d_post, d_align, d_stop, s);
+  if (persist) run_persistent(c, r, W.thr, s, t ? S_cap : 0);
+  else run_graph_decoder(c, B, T_max, S_cap, r, W.thr, max_ms, s);
+  run_postnet_scatter(c, B, T_max, S_cap, r, k.d_dec, k.d_post, k.d_align, k.d_stop, s, t ? &ml : nullptr);
   read_status(c, B, r, persist, fv, s);
-  report_rows(c, perm, h_steps, h_status);
+  report_rows(c, perm, t ? rsteps : k.run.h_steps, t ? rstatus : k.run.h_status);
+  for (int b = 0; t && b < B; ++b)
+    TTS_CHECK(rsteps[b] == tsteps[b], "teacher-forced decode: a row's step count (internal error)");
   if (fv)  // the caller's stream waits for the decode's outputs here, for the vocoder at finish
-    HIP_OK(hipStreamWaitEvent((hipStream_t)stream, c->ev_status, 0));
+    HIP_OK(hipStreamWaitEvent((hipStream_t)k.stream, c->ev_status, 0));
   else
-    leave(c, stream);
-  c->last_B = B;
-  c->last_T = T_max;
-  c->last_S = S_cap;
-  c->last_r = r;
-}
-
-// Teacher-forced decode (Tacotron2.forward in eval): taco_infer's steps with the prenet fed from the
-// ground-truth mel (teacher_prenet.hip + the persistent decoder's teacher variant), exactly
-// S_i = ceil(M_i / r) steps per row, raw stop logits, and the reference's output mask
-void ttsh::taco_forward(tts_ctx* c, const int64_t* ids, const int32_t* h_lens, int B, int T_max, int r,
-                        const float* d_mel, const int32_t* h_mel_lens, int M_max, const int64_t* d_spk_ids,
-                        const float* d_spk_emb, float* d_dec, float* d_post, float* d_align, float* d_stop,
-                        void* stream, const float* d_style) {
-  auto& M = c->taco;
-  TTS_CHECK(M.ready, "tacotron2 weights not finalized");
-  TTS_CHECK(M_max >= 1 && M_max <= (1 << 20) && r >= 1 && M_max % r == 0, "M_max must be a positive multiple of r");
-  TTS_CHECK(!M.windowing && !M.forward_attn && !M.graves,
-            "teacher-forced forward: attention windowing, forward attention and Graves attention are not implemented");
-  const int S_cap = M_max / r;
-  int32_t steps[BMAX], rsteps[BMAX], rstatus[BMAX];
-  TTS_CHECK(B >= 1 && B <= BMAX, "B must be in [1, 64]");
-  for (int b = 0; b < B; ++b) {
-    TTS_CHECK(h_mel_lens[b] >= 1 && h_mel_lens[b] <= M_max, "mel lens out of range");
-    steps[b] = (h_mel_lens[b] + r - 1) / r;
-  }
-  check_infer_args(M, h_lens, B, T_max, r, steps, S_cap);
-  taco_workspace(c, B, T_max, S_cap, r);
-  auto& W = c->tws;
-  grow<float>(W.teach, (size_t)S_cap * W.MT * 16 * 256, W.gen);
-  hipStream_t s = c->s;
-  enter(c, stream);
-  const std::vector<int> perm = stage_decode_order(c, h_lens, steps, B, nullptr, s);
-  W.thr = 0.5f;  // unused: a teacher-forced row never stops by its stop token
-  TTS_CHECK(use_persistent(c), "teacher-forced forward runs on the persistent decoder only (<= 64 utterances per "
-                               "call on a 256-CU device, TTS_DECODER=graph unset)");
-  stage_speakers(c, d_spk_ids, d_spk_emb, d_style, B, s);
-  run_encoder_penc(c, ids, B, T_max, s);
-  if (!W.pslot_cal) {
-    pick_barrier_blocks(reinterpret_cast<unsigned*>(W.pbar.p), PBAR_CAND, PMAX_LAUNCH, W.pslot, s);
-    W.pslot_cal = true;
-  }
-  fill_decoder_state(c, B, T_max, S_cap, r, true, s);
-  TeachArgs ta{};
-  ta.mel = d_mel;
-  ta.mel_b = (long)M_max * 80;
-  ta.map = W.map.i();
-  ta.max_steps = ctl_block(W)->max_steps;
-  ta.W1 = M.pre1.f();
-  ta.b1 = M.prenet_bn ? M.pre1_b0.f() : nullptr;
-  ta.teach = W.teach.f();
-  ta.B = B;
-  ta.Bp = W.MT * 16;
-  ta.r = r;
-  ta.steps = S_cap;
-  launch_teacher_prenet(ta, s);
-  c->dec_path = 1;
-  run_persistent(c, r, W.thr, s, S_cap);
-  MelLens ml{};
-  for (int i = 0; i < B; ++i) ml.M[i] = h_mel_lens[perm[i]];
-  run_postnet_scatter(c, B, T_max, S_cap, r, d_dec, d_post, d_align, d_stop, s, &ml);
-  read_status(c, B, r, true, nullptr, s);
-  report_rows(c, perm, rsteps, rstatus);
-  for (int b = 0; b < B; ++b) TTS_CHECK(rsteps[b] == steps[b], "teacher-forced decode: a row's step count (internal error)");
-  leave(c, stream);
+    leave(c, k.stream);
   c->last_B = B;
   c->last_T = T_max;
   c->last_S = S_cap;
@@ -1037,81 +822,13 @@ int tts_taco_forward_style(tts_ctx* c, const int64_t* d_ids, const int32_t* h_le
   return guarded_ctx(c, [&] {
     TTS_CHECK(c && d_ids && h_lens && d_mel && h_mel_lens && d_dec && d_post && d_align && d_stop, "null argument");
     DeviceGuard g(c->device);
-    with_x3_fallback(c, [&] {
-      taco_forward(c, d_ids, h_lens, B, T_max, r, d_mel, h_mel_lens, M_max, d_spk_ids, d_spk_emb, d_dec, d_post,
-                   d_align, d_stop, stream, d_style);
-    });
-  });
-}
-
-int tts_taco_gst_info(tts_ctx* c, int* gst_dim, int* num_tokens, int* query_uses_speaker) {
-  return guarded_ctx(c, [&] {
-    TTS_CHECK(gst_dim && num_tokens && query_uses_speaker, "null argument");
-    TTS_CHECK(c->taco.ready, "tacotron2 weights not finalized");
-    *gst_dim = c->taco.gst_dim;
-    *num_tokens = c->taco.gst_dim ? c->taco.gst_ntok : 0;
-    *query_uses_speaker = c->taco.gst_dim && c->taco.gst_es_q ? 1 : 0;
-  });
-}
-
-int tts_taco_style_mel(tts_ctx* c, const float* d_mel, const int32_t* h_lens, int B, int N_max, const float* d_spk_emb,
-                       float* d_style, void* stream) {
-  return guarded_ctx(c, [&] {
-    auto& M = c->taco;
-    TTS_CHECK(d_mel && h_lens && d_style, "null argument");
-    TTS_CHECK(M.ready && M.gst_dim, "the loaded tacotron2 model has no gst_layer");
-    TTS_CHECK(B >= 1 && B <= BMAX, "B must be in [1, 64]");
-    TTS_CHECK(N_max >= 1 && N_max <= (1 << 16), "N_max must be in [1, 65536]");
-    TTS_CHECK(!M.gst_es_q || d_spk_emb, "this model's style query takes the speaker embeddings: pass them");
-    GstLens lens{};
-    for (int b = 0; b < B; ++b) {
-      TTS_CHECK(h_lens[b] >= 1 && h_lens[b] <= N_max, "style mel lens out of range");
-      lens.v[b] = h_lens[b];
-    }
-    DeviceGuard g(c->device);
-    // layer 1's output (B, W1, 40, 32) and layer 2's (B, W2, 20, 32); the later, smaller layers alternate
-    const int W1 = (N_max + 1) / 2, W2 = (W1 + 1) / 2;
-    int W6 = W2;
-    for (int l = 2; l < 6; ++l) W6 = (W6 + 1) / 2;
-    c->gstws.a.ensure((size_t)B * W1 * 40 * 32 * 4);
-    c->gstws.b.ensure((size_t)B * W2 * 20 * 32 * 4);
-    enter(c, stream);
-    const float *cw[6], *cb[6];
-    for (int l = 0; l < 6; ++l) cw[l] = M.gst_cw[l].f(), cb[l] = M.gst_cb[l].f();
-    launch_gst_convs(d_mel, lens, B, N_max, cw, cb, c->gstws.a.f(), c->gstws.b.f(), c->s);
-    GstHeadArgs a{};
-    a.x = c->gstws.b.f();
-    a.xb = (long)W6 * 256;
-    a.lens = lens;
-    a.wihT = M.gst_wihT.f(), a.whhT = M.gst_whhT.f(), a.bih = M.gst_bih.f(), a.bhh = M.gst_bhh.f();
-    a.wqT = M.gst_wqT.f(), a.Kt = M.gst_K.f(), a.Vt = M.gst_V.f();
-    a.spk = M.gst_es_q ? d_spk_emb : nullptr;
-    a.Hg = M.gst_dim / 2, a.G = M.gst_dim, a.heads = M.gst_heads, a.ntok = M.gst_ntok, a.Es = M.gst_es_q;
-    a.scale = (float)std::sqrt((double)(M.gst_dim / M.gst_heads));
-    a.out = d_style;
-    launch_gst_head(a, B, c->s);
-    leave(c, stream);
-  });
-}
-
-int tts_taco_style_tokens(tts_ctx* c, const int32_t* h_token_ids, const float* h_weights, int n, float* d_style,
-                          void* stream) {
-  return guarded_ctx(c, [&] {
-    auto& M = c->taco;
-    TTS_CHECK(d_style && (n == 0 || (h_token_ids && h_weights)), "null argument");
-    TTS_CHECK(M.ready && M.gst_dim, "the loaded tacotron2 model has no gst_layer");
-    TTS_CHECK(n >= 0 && n <= GST_DICT_MAX, "at most 64 token weights");
-    GstTokenArgs a{};
-    a.n = n;
-    for (int i = 0; i < n; ++i) {
-      TTS_CHECK(h_token_ids[i] >= 0 && h_token_ids[i] < M.gst_ntok, "style token index out of range");
-      a.id[i] = h_token_ids[i];
-      a.w[i] = h_weights[i];
-    }
-    DeviceGuard g(c->device);
-    enter(c, stream);
-    launch_gst_tokens(a, M.gst_V.f(), M.gst_dim, M.gst_ntok, d_style, c->s);
-    leave(c, stream);
+    const TacoTeach teach{d_mel, h_mel_lens, M_max};
+    TacoCall k;
+    k.ids = d_ids, k.h_lens = h_lens, k.B = B, k.T_max = T_max, k.r = r, k.stream = stream;
+    k.d_spk_ids = d_spk_ids, k.d_spk_emb = d_spk_emb, k.d_style = d_style;
+    k.d_dec = d_dec, k.d_post = d_post, k.d_align = d_align, k.d_stop = d_stop;
+    k.teach = &teach;
+    with_x3_fallback(c, [&] { taco_run(c, k); });
   });
 }
 
@@ -1138,10 +855,12 @@ int tts_taco_infer_style(tts_ctx* c, const int64_t* d_ids, const int32_t* h_lens
     TTS_CHECK(c && d_ids && h_lens && h_max_steps && d_dec && d_post && d_align && d_stop && h_steps && h_status,
               "null argument");
     DeviceGuard g(c->device);
-    with_x3_fallback(c, [&] {
-      taco_infer(c, d_ids, h_lens, B, T_max, r, h_max_steps, S_cap, thr, d_dec, d_post, d_align, d_stop, h_steps,
-                 h_status, stream, d_spk_ids, d_spk_emb, nullptr, d_style);
-    });
+    TacoCall k;
+    k.ids = d_ids, k.h_lens = h_lens, k.B = B, k.T_max = T_max, k.r = r, k.stream = stream;
+    k.d_spk_ids = d_spk_ids, k.d_spk_emb = d_spk_emb, k.d_style = d_style;
+    k.d_dec = d_dec, k.d_post = d_post, k.d_align = d_align, k.d_stop = d_stop;
+    k.run = TacoFree{h_max_steps, S_cap, thr, h_steps, h_status};
+    with_x3_fallback(c, [&] { taco_run(c, k); });
   });
 }
 
@@ -1233,43 +952,5 @@ int tts_decoder_stats(tts_ctx* c, int* path, int* nlaunch, float* ms, int* steps
   });
 }
 
-int tts_time_decoder_kernel(tts_ctx* c, int which, int iters, float* ms_out) {
-  return guarded_ctx(c, [&] {
-    TTS_CHECK(c && ms_out && iters >= 1, "bad arguments");
-    TTS_CHECK(c->last_B > 0 && c->tws.graphs[c->tws.MT], "run tts_taco_infer first");
-    TTS_CHECK(c->tws.S_cap >= CHUNK + 2, "S_cap too small for timing");
-    DeviceGuard g(c->device);
-    auto& W = c->tws;
-    hipStream_t s = c->s;
-    // live state of the last decode, re-armed: base = 1, nothing done, unbounded max steps
-    DecCtlBlock ctl{};
-    ctl.ctl.base = 1;
-    std::fill(ctl.max_steps, ctl.max_steps + BMAX, 1 << 30);
-    hipEvent_t e0, e1;
-    HIP_OK(hipEventCreate(&e0));
-    HIP_OK(hipEventCreate(&e1));
-    HIP_OK(hipMemcpyAsync(W.ctl.p, &ctl, sizeof(ctl), hipMemcpyHostToDevice, s));
-    if (which == 0) enqueue_step(c, 0, 0, s, W.MT);  // warm-up
-    else HIP_OK(hipGraphLaunch(W.graphs[W.MT], s));
-    HIP_OK(hipMemcpyAsync(W.ctl.p, &ctl, sizeof(ctl), hipMemcpyHostToDevice, s));
-    HIP_OK(hipEventRecord(e0, s));
-    for (int i = 0; i < iters; ++i) {
-      if (which == 0) enqueue_step(c, 0, 0, s, W.MT);
-      else {
-        HIP_OK(hipGraphLaunch(W.graphs[W.MT], s));
-      }
-    }
-    HIP_OK(hipEventRecord(e1, s));
-    HIP_OK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIP_OK(hipEventElapsedTime(&ms, e0, e1));
-    *ms_out = which == 0 ? ms / iters : ms / (iters * CHUNK);
-    // leave the control block in a finished state
-    ctl.ctl.all_done = 1;
-    HIP_OK(hipMemcpy(W.ctl.p, &ctl, sizeof(ctl), hipMemcpyHostToDevice));
-    HIP_OK(hipEventDestroy(e0));
-    HIP_OK(hipEventDestroy(e1));
-  });
-}
 
 }  // extern "C"

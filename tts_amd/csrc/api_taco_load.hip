@@ -10,91 +10,6 @@
 
 using namespace ttsh;
 
-// Global Style Tokens (gst_layers.py): the reference encoder's convs with their BatchNorm2d (eval,
-// eps 1e-5) and bias folded in double, as [kt][kh][ci][co]; the GRU matrices transposed, W_ih's
-// columns reordered from the reference's [channel][mel bin] features to the kernels' [mel bin][channel];
-// W_query transposed; and the attention's keys and values, which depend on the weights alone:
-// K = tanh(tokens) W_key^T, V = tanh(tokens) W_value^T, (ntok, G) each. V's row k is also what a
-// {token k: 1} dict yields (one key: the softmax is 1).
-void ttsh::gst_load(tts_ctx* c) {
-  auto& M = c->taco;
-  const auto& h = c->taco_host;
-  const std::string P = "gst_layer.";
-  const auto& tok = need(h, P + "style_token_layer.style_tokens", {});
-  TTS_CHECK(tok.shape.size() == 2, "gst style_tokens must be (tokens, gst_embedding_dim / heads)");
-  const int ntok = (int)tok.shape[0], dk = (int)tok.shape[1];
-  const auto& wv = need(h, P + "style_token_layer.attention.W_value.weight", {});
-  TTS_CHECK(wv.shape.size() == 2 && wv.shape[1] == dk, "gst W_value must be (gst_embedding_dim, key dim)");
-  const int G = (int)wv.shape[0], Hg = G / 2;
-  TTS_CHECK(G == 128 || G == 256 || G == 512, "gst_embedding_dim must be 128, 256 or 512");
-  TTS_CHECK(dk >= 4 && G % dk == 0 && (G / dk == 2 || G / dk == 4 || G / dk == 8), "gst_num_heads must be 2, 4 or 8");
-  TTS_CHECK(ntok >= 1 && ntok <= GST_TOK_MAX, "gst_style_tokens must be in [1, 32]");
-  TTS_CHECK(M.spk_dim > G, "GST is built for multi-speaker models only (a speaker vector behind the style vector)");
-  const auto& wq = need(h, P + "style_token_layer.attention.W_query.weight", {});
-  TTS_CHECK(wq.shape.size() == 2 && wq.shape[0] == G && wq.shape[1] >= Hg, "gst W_query must be (G, G / 2 [+ Es])");
-  const int Kq = (int)wq.shape[1], Esq = Kq - Hg;
-  TTS_CHECK(Esq == 0 || Esq == M.spk_dim - G, "gst W_query: its speaker columns must match the speaker embedding dim");
-  TTS_CHECK(Esq % 4 == 0 && Esq <= GST_ES_MAX, "gst W_query: speaker embedding dim must be a multiple of 4, <= 1024");
-  const auto& wk = need(h, P + "style_token_layer.attention.W_key.weight", {G, dk}).d;
-  const int filt[7] = {1, 32, 32, 64, 64, 128, 128};
-  for (int l = 0; l < 6; ++l) {
-    const int ci_n = filt[l], co_n = filt[l + 1];
-    const std::string cn = P + "encoder.convs." + std::to_string(l), bn = P + "encoder.bns." + std::to_string(l);
-    const auto& w = need(h, cn + ".weight", {co_n, ci_n, 3, 3}).d;
-    const auto& b = need(h, cn + ".bias", {co_n}).d;
-    const auto& g_ = need(h, bn + ".weight", {co_n}).d;
-    const auto& be = need(h, bn + ".bias", {co_n}).d;
-    const auto& mu = need(h, bn + ".running_mean", {co_n}).d;
-    const auto& var = need(h, bn + ".running_var", {co_n}).d;
-    std::vector<float> wt((size_t)9 * ci_n * co_n), bt(co_n);
-    for (int co = 0; co < co_n; ++co) {
-      const double sc = (double)g_[co] / std::sqrt((double)var[co] + 1e-5);
-      bt[co] = (float)(((double)b[co] - mu[co]) * sc + be[co]);
-      for (int ci = 0; ci < ci_n; ++ci)
-        for (int k = 0; k < 9; ++k)
-          wt[((size_t)k * ci_n + ci) * co_n + co] = (float)(sc * w[((size_t)co * ci_n + ci) * 9 + k]);
-    }
-    M.gst_cw[l].upload(wt);
-    M.gst_cb[l].upload(bt);
-  }
-  {
-    const std::string rn = P + "encoder.recurrence.";
-    const auto& wih = need(h, rn + "weight_ih_l0", {3 * Hg, 256}).d;
-    const auto& whh = need(h, rn + "weight_hh_l0", {3 * Hg, Hg}).d;
-    std::vector<float> it((size_t)256 * 3 * Hg), ht((size_t)Hg * 3 * Hg);
-    for (int g = 0; g < 3 * Hg; ++g) {
-      for (int ch = 0; ch < 128; ++ch)
-        for (int hb = 0; hb < 2; ++hb) it[(size_t)(hb * 128 + ch) * 3 * Hg + g] = wih[(size_t)g * 256 + ch * 2 + hb];
-      for (int k = 0; k < Hg; ++k) ht[(size_t)k * 3 * Hg + g] = whh[(size_t)g * Hg + k];
-    }
-    M.gst_wihT.upload(it);
-    M.gst_whhT.upload(ht);
-    M.gst_bih.upload(need(h, rn + "bias_ih_l0", {3 * Hg}).d);
-    M.gst_bhh.upload(need(h, rn + "bias_hh_l0", {3 * Hg}).d);
-  }
-  std::vector<float> qt((size_t)Kq * G), kt((size_t)ntok * G), vt((size_t)ntok * G);
-  for (int j = 0; j < G; ++j)
-    for (int k = 0; k < Kq; ++k) qt[(size_t)k * G + j] = wq.d[(size_t)j * Kq + k];
-  for (int k = 0; k < ntok; ++k)
-    for (int j = 0; j < G; ++j) {
-      double ak = 0.0, av = 0.0;
-      for (int d = 0; d < dk; ++d) {
-        const double t = std::tanh((double)tok.d[(size_t)k * dk + d]);
-        ak += t * wk[(size_t)j * dk + d];
-        av += t * wv.d[(size_t)j * dk + d];
-      }
-      kt[(size_t)k * G + j] = (float)ak;
-      vt[(size_t)k * G + j] = (float)av;
-    }
-  M.gst_wqT.upload(qt);
-  M.gst_K.upload(kt);
-  M.gst_V.upload(vt);
-  M.gst_dim = G;
-  M.gst_heads = G / dk;
-  M.gst_ntok = ntok;
-  M.gst_es_q = Esq;
-}
-
 static void taco_finalize(tts_ctx* c, int num_chars, int r_init, int attn_norm) {
   auto& M = c->taco;
   M.graves = c->taco_host.count("decoder.attention.N_a.0.weight") > 0;

@@ -14,6 +14,9 @@
 #include <string>
 #include <vector>
 
+struct DecCtlBlock;  // decoder.h
+struct DecDev;
+
 namespace ttsh {
 
 constexpr int CHUNK = 8;  // decoder steps per captured graph (even: parity of t == parity of j)
@@ -444,14 +447,11 @@ struct tts_ctx {
   // the fused submissions' vocoders run on sv (TTS_VOC_STREAM=0: sv is s), behind their decode's
   // status event, so the next submission's Tacotron2 on s overlaps them. Each ticket slot has its own
   // device lengths and range flag (vslot: [NVT][BMAX] lengths, then NVT flags). Every other entry
-  // joins sv first (enter); a fused submission's Tacotron2 does not (in_submit).
+  // joins sv first (enter); a fused submission's Tacotron2 does not (enter's join_voc).
   hipStream_t sv = nullptr;
   hipEvent_t ev_sv = nullptr;  // after the last vocoder enqueued on sv
   bool sv_live = false;        // sv may hold work that s has not joined
-  bool in_submit = false;
   ttsh::DevBuf vslot;
-  unsigned* flag_override = nullptr;  // range flag of the vocoder being enqueued (x3_flag)
-  int* vlens_override = nullptr;      // device lengths of the vocoder being enqueued (run_generator)
 };
 
 namespace ttsh {
@@ -468,7 +468,6 @@ inline unsigned* vslot_flag(tts_ctx* c, int k) {
 // range flag for the split-f16 kernels of the current call, or null (fp32 kernels)
 inline unsigned* x3_flag(tts_ctx* c) {
   if (!c->gemm_x3) return nullptr;
-  if (c->flag_override) return c->flag_override;
   c->x3flag.ensure(4);
   return reinterpret_cast<unsigned*>(c->x3flag.p);
 }
@@ -486,7 +485,8 @@ struct DeviceGuard {
 
 // stream ordering with the caller's stream (nothing to wait for when all of its work is complete:
 // a server loop's stream holds only waits on this context's own finished events)
-void enter(tts_ctx* c, void* stream);
+// join_voc: wait for the fused submissions' vocoders on sv first (all but a fused submission's decode)
+void enter(tts_ctx* c, void* stream, bool join_voc = true);
 void leave(tts_ctx* c, void* stream);
 
 template <class T>
@@ -497,6 +497,17 @@ bool grow(DevBuf& b, size_t n, long& gen) {
   }
   return false;
 }
+
+// The fp32 re-run of work whose split-f16 kernels raised the range flag: counts the fallback and
+// keeps the context on the fp32 kernels for the guard's lifetime
+struct Fp32Rerun {
+  tts_ctx* c;
+  explicit Fp32Rerun(tts_ctx* c_) : c(c_) {
+    c->x3_fallbacks++;
+    c->gemm_x3 = false;
+  }
+  ~Fp32Rerun() { c->gemm_x3 = true; }
+};
 
 // Runs fn, which enqueues vocoder kernels on c->s; split-f16 kernels among them raise the
 // workspace's range flag when an operand falls outside the f16 range (split16.h). If it was
@@ -513,21 +524,14 @@ void with_x3_fallback(tts_ctx* c, F&& fn) {
   HIP_OK(hipMemsetAsync(flag, 0, 4, c->s));
   c->flag_read = false;
   fn();
-  if (!c->flag_read) {  // fn may have fetched it with its own status words (taco_infer)
+  if (!c->flag_read) {  // fn may have fetched it with its own status words (taco_run)
     HIP_OK(hipMemcpyAsync(&c->pinned[PIN_FLAG], flag, 4, hipMemcpyDeviceToHost, c->s));
     HIP_OK(hipStreamSynchronize(c->s));
   }
   c->flag_read = false;
   if (c->pinned[PIN_FLAG]) {
-    c->x3_fallbacks++;
-    c->gemm_x3 = false;
-    try {
-      fn();
-    } catch (...) {
-      c->gemm_x3 = true;
-      throw;
-    }
-    c->gemm_x3 = true;
+    Fp32Rerun f32(c);
+    fn();
   }
 }
 
@@ -571,9 +575,15 @@ int ctx_call(tts_ctx* c, void* stream, Pre&& pre, F&& fn) {
   });
 }
 
-// --- Tacotron2: api_taco_load.hip (workspace, per-r projection fold), api_taco.hip (taco_infer)
+// --- Tacotron2: api_taco_load.hip (workspace, per-r projection fold), api_taco.hip (taco_run),
+// api_taco_graph.hip (the captured-graph decoder), api_gst.hip (Global Style Tokens)
 void taco_workspace(tts_ctx* c, int B, int T_max, int S_cap, int r);
 void build_pj(tts_ctx* c, int r);
+// the decoder's control block and per-launch device view (decoder.h), shared by both decoders
+DecCtlBlock* ctl_block(const TacoWS& W);
+DecDev make_dev(tts_ctx* c, int Bact);
+// the decode as captured CHUNK-step graphs (decoder.hip's per-step kernels), polled by the host
+void run_graph_decoder(tts_ctx* c, int B, int T_max, int S_cap, int r, float thr, int max_ms, hipStream_t s);
 // the vocoder half of a fused Tacotron2 + MB-MelGAN call: the decode's status kernel writes the
 // vocoder's lengths into vlens (device, caller order), and enqueue() launches the vocoder on them
 // before the host waits for the status words, so the GPU runs both models back to back
@@ -586,31 +596,59 @@ struct FusedVoc {
   std::function<void()> enqueue;
 };
 
-void taco_infer(tts_ctx* c, const int64_t* ids, const int32_t* h_lens, int B, int T_max, int r,
-                const int32_t* h_max_steps, int S_cap, float thr, float* d_dec, float* d_post, float* d_align,
-                float* d_stop, int32_t* h_steps, int32_t* h_status, void* stream,
-                const int64_t* d_spk_ids = nullptr, const float* d_spk_emb = nullptr, const FusedVoc* fv = nullptr,
-                const float* d_style = nullptr);
+// One Tacotron2 call, filled once by its extern "C" entry point (d_*: device, h_*: host; rows in the
+// caller's order). Free-running part: a row stops at its stop token (thr) or after h_max_steps[b] <=
+// S_cap steps, h_steps / h_status receive the rows' results; fv: a fused call's vocoder, or null.
+struct TacoFree {
+  const int32_t* h_max_steps = nullptr;
+  int S_cap = 0;
+  float thr = 0.5f;
+  int32_t *h_steps = nullptr, *h_status = nullptr;
+  const FusedVoc* fv = nullptr;
+};
+// Teacher-forced part (Tacotron2.forward in eval): d_mel (B, M_max, 80), M_max a multiple of r; row b
+// runs ceil(h_mel_lens[b] / r) steps.
+struct TacoTeach {
+  const float* d_mel = nullptr;
+  const int32_t* h_mel_lens = nullptr;
+  int M_max = 0;
+};
+struct TacoCall {
+  const int64_t* ids = nullptr;
+  const int32_t* h_lens = nullptr;
+  int B = 0, T_max = 0, r = 0;
+  const int64_t* d_spk_ids = nullptr;  // speaker ids or embeddings: multi-speaker models
+  const float* d_spk_emb = nullptr;
+  const float* d_style = nullptr;  // (B, gst_dim), or null (zeros): GST models only
+  float *d_dec = nullptr, *d_post = nullptr, *d_align = nullptr, *d_stop = nullptr;
+  void* stream = nullptr;
+  TacoFree run;                      // read when teach is null
+  const TacoTeach* teach = nullptr;  // set: the teacher-forced decode
+};
+void taco_run(tts_ctx* c, const TacoCall& k);
 
-// Tacotron2.forward in eval (tts_taco_forward): d_mel (B, M_max, 80), M_max a multiple of r
-void taco_forward(tts_ctx* c, const int64_t* ids, const int32_t* h_lens, int B, int T_max, int r, const float* d_mel,
-                  const int32_t* h_mel_lens, int M_max, const int64_t* d_spk_ids, const float* d_spk_emb, float* d_dec,
-                  float* d_post, float* d_align, float* d_stop, void* stream, const float* d_style = nullptr);
-// d_style (B, gst_dim), caller row order, or null (zeros): GST models only
-
-// Global Style Tokens, load: gst_layer.* folded and uploaded, key / value tables built (api_taco_load.hip)
+// Global Style Tokens, load: gst_layer.* folded and uploaded, key / value tables built (api_gst.hip)
 void gst_load(tts_ctx* c);
 
 // --- MelGAN: api_melgan.hip, for the fused path
+// One vocoder run. dev_lens: the device lengths buffer already holds the lengths (a fused call's
+// decode wrote them, checked there against vocoder_min_len); h_lens are then per-row upper bounds,
+// used for tile counts. A fused submission's vocoder brings its ticket slot's buffers.
+struct VocCall {
+  const float* mel = nullptr;
+  const int64_t* mel_strides = nullptr;  // {batch, channel, frame}, or null: (B, in_ch, M_max) contiguous
+  const int32_t* h_lens = nullptr;
+  int B = 0, M_max = 0, pad = 0;
+  bool dev_lens = false;
+  hipStream_t s = nullptr;   // null: c->s
+  int* d_lens = nullptr;     // device lengths buffer; null: the workspace's
+  unsigned* flag = nullptr;  // range flag of the split-f16 kernels; null: the context's
+};
 // returns total upsampling factor; writes bands (B, out_ch, up*(M_max+2pad)) into `out`
-// dev_lens: W.lens already holds the lengths on the device (a fused call's decode wrote them,
-// checked there against vocoder_min_len); h_lens are then per-row upper bounds, used for tile counts
-int run_generator(tts_ctx* c, const float* mel, const int32_t* h_lens, int B, int M_max, int pad, float* out,
-                  hipStream_t s, GenTail* tail = nullptr, const int64_t* mel_strides = nullptr, bool dev_lens = false);
-// MultibandMelganGenerator.inference body on s (default c->s): generator, output conv and PQMF synthesis into
+int run_generator(tts_ctx* c, const VocCall& v, float* out, GenTail* tail = nullptr);
+// MultibandMelganGenerator.inference body: generator, output conv and PQMF synthesis into
 // d_wav (B, 1, hop * (M_max + 2 pad)), rows zero past their own length
-void mbmelgan_body(tts_ctx* c, const float* d_mel, const int64_t* mel_strides, const int32_t* h_lens, int B,
-                   int M_max, int pad, float* d_wav, bool dev_lens = false, hipStream_t s = nullptr);
+void mbmelgan_body(tts_ctx* c, const VocCall& v, float* d_wav);
 // the shortest mel (frames) the vocoder accepts at inference padding pad: run_generator's checks
 int vocoder_min_len(const MelganModel& G, int pad);
 
