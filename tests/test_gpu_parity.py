@@ -2002,6 +2002,53 @@ def test_pwgan_lj_batch_full_size_batched_equals_single():
             assert not yb[i, 0, n:].any(), i
 
 
+_PWGAN_ROWS = {}
+
+
+def _pwgan_many_rows():
+    """The synthetic ParallelWaveGAN, 130 mels of 1 + (2 b) % 3 frames (rows 64, 65, 66 are 3, 2, 1
+    frames long where rows 0, 1, 2 are 1, 3, 2), explicit noise, and every row's B = 1 result; built
+    once for both batch sizes."""
+    if not _PWGAN_ROWS:
+        from tts_amd import ParallelWaveganGenerator
+        from tts_amd.spec import PwganConfig, pwgan_spec
+        _dev()
+        sd = synth_state_dict(pwgan_spec(PwganConfig()), 5)
+        g = ParallelWaveganGenerator(inference_padding=0)
+        g.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+        g = g.cuda().eval()
+        M = [1 + (b * 2) % 3 for b in range(130)]
+        rs = np.random.RandomState(11)
+        mel = np.zeros((130, 80, 3), np.float32)
+        for i, m in enumerate(M):
+            mel[i, :, :m] = rs.normal(0, 1, (80, m))
+        noise = torch.randn(130, 1, 3 * 256, generator=torch.Generator().manual_seed(4)).cuda()
+        melt = torch.from_numpy(mel).cuda()
+        # B = 1 calls at the batch's mel capacity (3 frames) and the row's own length: the capacity is the
+        # mel's channel stride, which picks the first conv's kernel (a 1-frame mel takes the fp32 conv)
+        single = [g.inference(melt[i:i + 1], lengths=[m], noise=noise[i:i + 1]).cpu().numpy()[0, 0]
+                  for i, m in enumerate(M)]
+        _PWGAN_ROWS.update(g=g, M=M, mel=melt, noise=noise, single=single)
+    return _PWGAN_ROWS
+
+
+@pytest.mark.parametrize("B", [65, 130])
+def test_pwgan_more_than_64_rows_batched_equals_single(B):
+    """tts_pwgan_infer takes more than 64 rows, so the rows' lengths reach the device in more than
+    one group of 64: every row of a B = 65 / 130 call (1 to 3 mel frames, lengths that differ across
+    the groups) is bit-identical to its own B = 1 call on the same mel and noise, and zero past its
+    length."""
+    r = _pwgan_many_rows()
+    g, M = r["g"], r["M"][:B]
+    yb = g.inference(r["mel"][:B], lengths=M, noise=r["noise"][:B].contiguous()).cpu().numpy()
+    assert yb.shape == (B, 1, 3 * 256)
+    for i, m in enumerate(M):
+        n = m * 256
+        assert r["single"][i].shape == (3 * 256,)
+        assert np.array_equal(yb[i, 0, :n], r["single"][i][:n]), i
+        assert yb[i, 0, n - 256:n].any() and not yb[i, 0, n:].any(), i
+
+
 def test_c5_chained_shard_vs_oracle_chain():
     """Config C5's per-GPU shard as ONE chained GPU run (tools/c5_bench.py's models and workload):
     GE2E SpeakerEncoder.inference on 16 reference mels (160 frames x 40) -> their 256-d embeddings into

@@ -542,3 +542,36 @@ def test_runtime_switch_table_matches_switches_header():
               if f != "switches.h" and os.path.isfile(os.path.join(csrc, f))
               and "getenv" in open(os.path.join(csrc, f), errors="ignore").read()]
     assert others == [], others
+
+
+# every synchronous or one-off host-to-device copy the library may make: (file, text of the line) -> why
+_H2D_ALLOWED = {
+    ("host.h", "HIP_OK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));"):
+        "DevBuf::upload: synchronous weight and table uploads at load time",
+    ("api_core.hip", "HIP_OK(hipMemcpy(L.W16.p, w16.data(), w16.size() * 2, hipMemcpyHostToDevice));"):
+        "pack_conv / pack_conv_x3_only: the split-f16 weights, synchronous, at load time",
+    ("api_taco.hip", "HIP_OK(hipMemcpyAsync(W.fwd_u.p, half.data(), 64 * 4, hipMemcpyHostToDevice, s));"):
+        "forward attention's initial u = 0.5: the source is a static const array",
+    ("api_taco_graph.hip", "HIP_OK(hipMemcpyAsync(W.ctl.p, &ctl, sizeof(ctl), hipMemcpyHostToDevice, s));"):
+        "tts_time_decoder_kernel: the timing entry re-arms the control block, and synchronises before it returns",
+    ("api_taco_graph.hip", "HIP_OK(hipMemcpy(W.ctl.p, &ctl, sizeof(ctl), hipMemcpyHostToDevice));"):
+        "tts_time_decoder_kernel: synchronous restore of the control block",
+}
+
+
+def test_host_to_device_copies_are_allow_listed():
+    """Per-call row arrays (lengths, ids) reach the device as kernel arguments (put_rows, RowInts), never
+    through a copy from a host buffer that may die or stall the stream: every line of the library that
+    names hipMemcpyHostToDevice is one of the listed load-time or static-source copies."""
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tts_amd", "csrc")
+    seen = set()
+    for name in sorted(os.listdir(csrc)):
+        if not name.endswith((".hip", ".h")):
+            continue
+        for no, line in enumerate(open(os.path.join(csrc, name)), 1):
+            if "hipMemcpyHostToDevice" in line:
+                key = (name, line.strip())
+                assert key in _H2D_ALLOWED, f"{name}:{no}: host-to-device copy outside the allow-list: {line.strip()}"
+                seen.add(key)
+    assert seen == set(_H2D_ALLOWED), f"allow-list entries that match nothing: {set(_H2D_ALLOWED) - seen}"
+    assert all(reason for reason in _H2D_ALLOWED.values())

@@ -22,12 +22,6 @@ int async_call(tts_ctx* c, void* stream, Pre&& pre, F&& fn) {
   });
 }
 
-GlLens lens_arg(const int32_t* h_lens, int B) {
-  GlLens L{};
-  for (int b = 0; b < B; ++b) L.v[b] = h_lens[b];
-  return L;
-}
-
 // twiddles e^{-2 pi i m / 1024} and the periodic Hann window of win_length points, centred in
 // 1024 as torch.stft pads it; computed in double, uploaded once per win_length
 void gl_tables(tts_ctx* c, int win_length) {
@@ -100,7 +94,7 @@ int tts_stft_mag(tts_ctx* c, const float* d_wav, const int32_t* h_nsamples, int 
         AudioWS& A = c->aws;
         stft_tables(c, n_fft, win_length);
         const int wlo = (n_fft - win_length) / 2, whi = wlo + win_length;
-        launch_stft_frames(n_fft == 1024 && algo != 2, d_wav, L_max, lens_arg(h_nsamples, B), B, M_max, n_fft,
+        launch_stft_frames(n_fft == 1024 && algo != 2, d_wav, L_max, row_ints(h_nsamples, B), B, M_max, n_fft,
                            hop_length, wlo, whi, preemphasis, A.sW.f(), A.swin.f(), d_mag, c->s);
       });
 }
@@ -117,11 +111,10 @@ int tts_mag_to_feature(tts_ctx* c, const float* d_mag, const int32_t* h_lens, in
         TTS_CHECK(n_freq >= 1 && n_freq <= 1025, "mag_to_feature: 1 <= n_freq <= 1025");
         TTS_CHECK(n_out >= 1 && n_out <= 1025, "mag_to_feature: 1 <= n_out <= 1025");
         TTS_CHECK(d_basis || n_out == n_freq, "mag_to_feature: without a basis n_out must equal n_freq");
-        for (int b = 0; b < B; ++b)
-          TTS_CHECK(h_lens[b] >= 0 && h_lens[b] <= M_max, "mag_to_feature: h_lens[b] outside [0, M_max]");
+        check_rows(h_lens, B, 0, M_max, "mag_to_feature: h_lens[b] outside [0, M_max]");
       },
       [&] {
-        launch_mag_to_feature(d_mag, lens_arg(h_lens, B), B, M_max, n_freq, n_out, d_basis, spec_gain, d_scale,
+        launch_mag_to_feature(d_mag, row_ints(h_lens, B), B, M_max, n_freq, n_out, d_basis, spec_gain, d_scale,
                               d_offset, clip_lo, clip_hi, use_clip, d_out, c->s);
       });
 }
@@ -138,11 +131,10 @@ int tts_mel_to_linear(tts_ctx* c, const float* d_mel, const int32_t* h_lens, int
         TTS_CHECK(M_max >= 1 && n_freq >= 1, "mel_to_linear: M_max and n_freq must be positive");
         TTS_CHECK(n_mels >= 1 && n_mels <= 512, "mel_to_linear: 1 <= n_mels <= 512");
         TTS_CHECK(spec_gain != 0.f, "mel_to_linear: spec_gain must not be 0");
-        for (int b = 0; b < B; ++b)
-          TTS_CHECK(h_lens[b] >= 0 && h_lens[b] <= M_max, "mel_to_linear: h_lens[b] outside [0, M_max]");
+        check_rows(h_lens, B, 0, M_max, "mel_to_linear: h_lens[b] outside [0, M_max]");
       },
       [&] {
-        launch_mel_to_linear(d_mel, lens_arg(h_lens, B), B, M_max, n_mels, n_freq, d_inv_basis, d_scale, d_offset,
+        launch_mel_to_linear(d_mel, row_ints(h_lens, B), B, M_max, n_mels, n_freq, d_inv_basis, d_scale, d_offset,
                              clip_lo, clip_hi, use_clip, spec_gain, power, d_S, c->s);
       });
 }
@@ -172,7 +164,7 @@ int tts_griffin_lim(tts_ctx* c, const float* d_S, const int32_t* h_lens, int B, 
         A.fa.ensure(frames);
         A.fb.ensure(frames);
         A.env.ensure((size_t)B * env_stride * sizeof(float));
-        const GlLens L = lens_arg(h_lens, B);
+        const RowInts L = row_ints(h_lens, B);
         const int wlo = (1024 - win_length) / 2, whi = wlo + win_length;
         float *cur = A.fa.f(), *nxt = A.fb.f();
         launch_gl_env(A.env.f(), A.win.f(), L, B, M_max, hop_length, wlo, whi, env_stride, c->s);

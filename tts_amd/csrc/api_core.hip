@@ -13,6 +13,31 @@ void tts_set_error(const std::string& m) { g_err = m; }
 
 namespace ttsh {
 
+__global__ void put_rows_kernel(int* dst, RowInts r, int n) {
+  if ((int)threadIdx.x < n) dst[threadIdx.x] = r.v[threadIdx.x];
+}
+
+const int* put_rows(int* dst, const int32_t* h, int n, hipStream_t s) {
+  for (int o = 0; o < n; o += BMAX) {
+    const int m = std::min(BMAX, n - o);
+    put_rows_kernel<<<1, BMAX, 0, s>>>(dst + o, row_ints(h + o, m), m);
+    HIP_OK(hipGetLastError());
+  }
+  return dst;
+}
+const int* put_rows(DevBuf& dst, const int32_t* h, int n, hipStream_t s) {
+  ensure<int>(dst, n);
+  return put_rows(dst.i(), h, n, s);
+}
+const int* fill_rows(DevBuf& dst, int value, int n, hipStream_t s) {
+  const std::vector<int32_t> h(n, value);
+  return put_rows(dst, h.data(), n, s);
+}
+
+void check_rows(const int32_t* h, int n, long lo, long hi, const std::string& msg) {
+  for (int b = 0; b < n; ++b) TTS_CHECK(h[b] >= lo && h[b] <= hi, msg);
+}
+
 void upload_split_rows(DevBuf& d, const std::vector<float>& w, int rows, int K) {
   bool ok = rows % 16 == 0 && K % 32 == 0 && w.size() == (size_t)rows * K;
   for (float v : w) ok &= std::fabs(v) < F16_RANGE;

@@ -138,89 +138,51 @@ void ge2e_infer(tts_ctx* c, const float* d_x, const int32_t* h_lens, int B, int 
   TTS_CHECK(G.ready, "speaker encoder weights not finalized");
   TTS_CHECK(B >= 1 && B <= 64, "speaker encoder: B must be in [1, 64]");
   TTS_CHECK(T_max >= 1 && T_max <= 100000, "speaker encoder: bad T_max");
-  for (int b = 0; b < B; ++b) TTS_CHECK(h_lens[b] >= 1 && h_lens[b] <= T_max, "speaker encoder: lens out of range");
+  check_rows(h_lens, B, 1, T_max, "speaker encoder: lens out of range");
   hipStream_t s = c->s;
   const int H = G.H;
-  long gen = 0;
-  grow<float>(W.x, (size_t)B * T_max * G.in_pad, gen);
-  grow<int>(W.lens, 64, gen);
-  grow<float>(W.g, (size_t)B * T_max * 4 * H, gen);
-  grow<float>(W.o, (size_t)B * T_max * H, gen);
-  grow<float>(W.p, (size_t)B * T_max * G.proj, gen);
-  grow<unsigned>(W.bar, BAR_WORDS, gen);
-  grow<float>(W.hbuf, (size_t)2 * 64 * H, gen);
-  std::vector<int> lens(h_lens, h_lens + B);
-  HIP_OK(hipMemcpyAsync(W.lens.p, lens.data(), B * 4, hipMemcpyHostToDevice, s));
+  ensure<float>(W.x, (size_t)B * T_max * G.in_pad);
+  ensure<int>(W.lens, 64);
+  ensure<float>(W.g, (size_t)B * T_max * 4 * H);
+  ensure<float>(W.o, (size_t)B * T_max * H);
+  ensure<float>(W.p, (size_t)B * T_max * G.proj);
+  ensure<unsigned>(W.bar, BAR_WORDS);
+  ensure<float>(W.hbuf, (size_t)2 * 64 * H);
+  const int* dl = put_rows(W.lens, h_lens, B, s);
   pad_channels_kernel<<<1024, 256, 0, s>>>(d_x, G.in_dim, G.in_pad, (long)B * T_max, W.x.f());
   HIP_OK(hipGetLastError());
   const float* in = W.x.f();
   int din = G.in_pad;
+  // gates_in = x W_ih^T + b of layer l (time-major rows, K = 1), and the layer's Linear
+  auto gates = [&](int l) {
+    run_conv(G.gin[l], conv_call(c, dl, B, T_max).in(in, btc(T_max, din), din).to(W.g.f(), btc(T_max, 4 * H)), s);
+  };
+  auto project = [&](int l) {
+    run_conv(G.proj_l[l], conv_call(c, dl, B, T_max).in(W.o.f(), btc(T_max, H), H).to(W.p.f(), btc(T_max, G.proj)), s);
+  };
   // all layers in one persistent launch (encoder.hip ge2e_pipe_kernel); TTS_GE2E_PIPE=0 keeps
   // one launch per layer with the input projections as convs
   const bool pipe_env = sw::ge2e_pipe();
   bool piped = false;
   if (pipe_env && c->gemm_x3 && G.pipe_ok && B <= 16) {
-    ConvCall cc;  // layer-0 input gates
-    cc.lens = W.lens.i();
-    cc.B = B;
-    cc.oflow = x3_flag(c);
-    cc.max_q = T_max;
-    cc.s[0] = src_of(in, (long)T_max * din, 1, din, din, 0);
-    cc.out = W.g.f();
-    cc.ob = (long)T_max * 4 * H;
-    cc.oc = 1;
-    cc.ot = 4 * H;
-    run_conv(G.gin[0], cc, s);
+    gates(0);
     const uint16_t* w16[4] = {nullptr, nullptr, nullptr, nullptr};
     const float* bias[4] = {nullptr, nullptr, nullptr, nullptr};
     for (int l = 0; l < G.nl; ++l) {
       w16[l] = l == 0 ? G.whh16[0].h() : G.wpipe[l].h();
       bias[l] = l == 0 ? nullptr : G.bpipe[l].f();
     }
-    piped = launch_ge2e_pipe(w16, bias, G.nl, W.g.f(), W.lens.i(), T_max, B, W.hbuf.f(),
-                             reinterpret_cast<unsigned*>(W.bar.p), W.o.f(), s);
-    if (piped && G.with_proj) {  // the last layer's Linear
-      ConvCall cp;
-      cp.lens = W.lens.i();
-      cp.B = B;
-      cp.oflow = x3_flag(c);
-      cp.max_q = T_max;
-      cp.s[0] = src_of(W.o.f(), (long)T_max * H, 1, H, H, 0);
-      cp.out = W.p.f();
-      cp.ob = (long)T_max * G.proj;
-      cp.oc = 1;
-      cp.ot = G.proj;
-      run_conv(G.proj_l[G.nl - 1], cp, s);
-    }
+    piped = launch_ge2e_pipe(w16, bias, G.nl, W.g.f(), dl, T_max, B, W.hbuf.f(), reinterpret_cast<unsigned*>(W.bar.p),
+                             W.o.f(), s);
+    if (piped && G.with_proj) project(G.nl - 1);  // the last layer's Linear
   }
   for (int l = 0; l < G.nl && !piped; ++l) {
-    ConvCall cc;  // gates_in = x W_ih^T + b  (time-major rows, K = 1)
-    cc.lens = W.lens.i();
-    cc.B = B;
-    cc.oflow = x3_flag(c);
-    cc.max_q = T_max;
-    cc.s[0] = src_of(in, (long)T_max * din, 1, din, din, 0);
-    cc.out = W.g.f();
-    cc.ob = (long)T_max * 4 * H;
-    cc.oc = 1;
-    cc.ot = 4 * H;
-    run_conv(G.gin[l], cc, s);
-    const bool ok = launch_lstm768_persist(W.g.f(), G.whh[l].f(), c->gemm_x3 ? G.whh16[l].h() : nullptr, W.lens.i(),
-                                           T_max, B, W.hbuf.f(),
-                                           reinterpret_cast<unsigned*>(W.bar.p), W.o.f(), s);
+    gates(l);
+    const bool ok = launch_lstm768_persist(W.g.f(), G.whh[l].f(), c->gemm_x3 ? G.whh16[l].h() : nullptr, dl, T_max, B,
+                                           W.hbuf.f(), reinterpret_cast<unsigned*>(W.bar.p), W.o.f(), s);
     TTS_CHECK(ok, "speaker encoder: cooperative launch unavailable");
     if (G.with_proj) {
-      ConvCall cp;
-      cp.lens = W.lens.i();
-      cp.B = B;
-      cp.oflow = x3_flag(c);
-      cp.max_q = T_max;
-      cp.s[0] = src_of(W.o.f(), (long)T_max * H, 1, H, H, 0);
-      cp.out = W.p.f();
-      cp.ob = (long)T_max * G.proj;
-      cp.oc = 1;
-      cp.ot = G.proj;
-      run_conv(G.proj_l[l], cp, s);
+      project(l);
       in = W.p.f();
       din = G.proj;
     } else {
@@ -229,10 +191,10 @@ void ge2e_infer(tts_ctx* c, const float* d_x, const int32_t* h_lens, int B, int 
     }
   }
   if (G.with_proj)
-    ge2e_final_kernel<<<B, 256, 0, s>>>(W.p.f(), (long)T_max * G.proj, G.proj, W.lens.i(), T_max, nullptr, nullptr,
+    ge2e_final_kernel<<<B, 256, 0, s>>>(W.p.f(), (long)T_max * G.proj, G.proj, dl, T_max, nullptr, nullptr,
                                         G.proj, d_out);
   else
-    ge2e_final_kernel<<<B, 256, 0, s>>>(W.o.f(), (long)T_max * H, H, W.lens.i(), T_max, G.lin_w.f(), G.lin_b.f(),
+    ge2e_final_kernel<<<B, 256, 0, s>>>(W.o.f(), (long)T_max * H, H, dl, T_max, G.lin_w.f(), G.lin_b.f(),
                                         G.proj, d_out);
   HIP_OK(hipGetLastError());
   HIP_OK(hipStreamSynchronize(s));

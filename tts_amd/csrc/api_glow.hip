@@ -291,13 +291,13 @@ void glow_encode(tts_ctx* c, const int64_t* d_ids, const int32_t* h_lens, const 
   auto& W = c->glws;
   TTS_CHECK(G.ready, "glow weights not finalized");
   TTS_CHECK(B >= 1 && B <= 64 && T >= 1 && T <= 4096, "glow: bad sizes");
-  for (int b = 0; b < B; ++b) TTS_CHECK(h_lens[b] >= 1 && h_lens[b] <= T, "glow: lens out of range");
+  check_rows(h_lens, B, 1, T, "glow: lens out of range");
   if (h_spk) {
     // the reference looks g up in emb_g (absent unless num_speakers > 1) and feeds it to every WN
     // cond_layer (absent unless c_in_channels > 0): glow_tts.py:160, glow.py:119-120
     TTS_CHECK(G.n_spk > 1, "glow: speaker ids given but the model has no emb_g (num_speakers <= 1)");
     TTS_CHECK(G.c_in > 0, "glow: speaker ids given but the model has no cond_layer (c_in_channels = 0)");
-    for (int b = 0; b < B; ++b) TTS_CHECK(h_spk[b] >= 0 && h_spk[b] < G.n_spk, "glow: speaker id out of range");
+    check_rows(h_spk, B, 0, G.n_spk - 1, "glow: speaker id out of range");
   } else {
     // without g the reference's duration predictor reads x alone (encoder.py:136), which its
     // conv_1 rejects when it was built for hidden + c_in_channels inputs
@@ -305,72 +305,44 @@ void glow_encode(tts_ctx* c, const int64_t* d_ids, const int32_t* h_lens, const 
   }
   hipStream_t s = c->s;
   const int H = G.H, C = G.C, F = G.Fdp;
-  long gen = 0;
-  grow<int>(W.lens, 64, gen);
-  grow<int>(W.ylens, 64, gen);
-  grow<int>(W.klens, 64, gen);
-  grow<float>(W.xa, (size_t)B * 2 * H * T, gen);
-  grow<float>(W.xb, (size_t)B * H * T, gen);
-  grow<float>(W.h2, (size_t)B * 2 * H * T, gen);
-  grow<float>(W.hdp, (size_t)B * F * T, gen);
-  grow<float>(W.logw, (size_t)B * T, gen);
-  grow<float>(W.cum, (size_t)B * T, gen);
-  grow<float>(W.wceil, (size_t)B * T, gen);
-  grow<float>(W.om, (size_t)B * C * T, gen);
-  if (G.tfm) grow<float>(W.big, (size_t)B * 768 * T, gen);
+  ensure<int>(W.lens, 64);
+  ensure<int>(W.ylens, 64);
+  ensure<int>(W.klens, 64);
+  ensure<float>(W.xa, (size_t)B * 2 * H * T);
+  ensure<float>(W.xb, (size_t)B * H * T);
+  ensure<float>(W.h2, (size_t)B * 2 * H * T);
+  ensure<float>(W.hdp, (size_t)B * F * T);
+  ensure<float>(W.logw, (size_t)B * T);
+  ensure<float>(W.cum, (size_t)B * T);
+  ensure<float>(W.wceil, (size_t)B * T);
+  ensure<float>(W.om, (size_t)B * C * T);
+  if (G.tfm) ensure<float>(W.big, (size_t)B * 768 * T);
   W.B = B;
   W.Tx = T;
   W.has_g = h_spk != nullptr;
-  std::vector<int> lens(h_lens, h_lens + B);
-  W.h_xlens = lens;  // glow_align checks its mel lengths against them
-  HIP_OK(hipMemcpyAsync(W.lens.p, lens.data(), B * 4, hipMemcpyHostToDevice, s));
-  const int* dl = W.lens.i();
+  W.h_xlens.assign(h_lens, h_lens + B);  // glow_align checks its mel lengths against them
+  const int* dl = put_rows(W.lens, h_lens, B, s);
   if (W.has_g) {
     // g, then every WN layer's gate bias cond_layer(g) as one (B, flows * wn_layers * 2H) 1x1 conv
     // over a length-1 sequence
     const int NC = G.flows * G.wn_layers * 2 * H;
-    grow<int>(W.spk, 64, gen);
-    grow<float>(W.g, (size_t)B * G.c_pad, gen);
-    grow<float>(W.gcond, (size_t)B * NC, gen);
+    ensure<int>(W.spk, 64);
+    ensure<float>(W.g, (size_t)B * G.c_pad);
+    ensure<float>(W.gcond, (size_t)B * NC);
     if (!W.ones.p) {
       std::vector<int> one(64, 1);
       W.ones.upload(one);
     }
-    W.h_spk.assign(h_spk, h_spk + B);
-    HIP_OK(hipMemcpyAsync(W.spk.p, W.h_spk.data(), B * 4, hipMemcpyHostToDevice, s));
-    launch_glow_speaker(W.spk.i(), G.emb_g.f(), G.c_in, G.c_pad, W.g.f(), B, s);
-    ConvCall cc;
-    cc.lens = W.ones.i();
-    cc.B = B;
-    cc.oflow = x3_flag(c);
-    cc.max_q = 1;
-    cc.s[0] = src_of(W.g.f(), G.c_pad, 1, 1, G.c_pad, 0);
-    cc.out = W.gcond.f();
-    cc.ob = NC;
-    cc.oc = 1;
-    cc.ot = 1;
-    run_conv(G.cond, cc, s);
+    launch_glow_speaker(put_rows(W.spk, h_spk, B, s), G.emb_g.f(), G.c_in, G.c_pad, W.g.f(), B, s);
+    run_conv(G.cond, conv_call(c, W.ones.i(), B, 1).in(W.g.f(), bct(G.c_pad, 1), G.c_pad).to(W.gcond.f(), bct(NC, 1)), s);
   }
   float* x = W.xa.f();   // (B, H, T) current activations
   float* x2 = W.xb.f();  // ping-pong
   launch_glow_embed(d_ids, T, G.emb.f(), G.num_chars, H, dl, x, B, s);
   auto conv = [&](const ConvLayer& L, const float* in, int cin, float* out, int cout, int epi,
                   const float* resid = nullptr) {
-    ConvCall cc;
-    cc.lens = dl;
-    cc.B = B;
-    cc.oflow = x3_flag(c);
-    cc.max_q = T;
-    cc.s[0] = src_of(in, (long)cin * T, T, 1, cin, 0);
-    cc.out = out;
-    cc.ob = (long)cout * T;
-    cc.oc = T;
-    cc.ot = 1;
+    ConvCall cc = conv_call(c, dl, B, T).in(in, bct(cin, T), cin).to(out, bct(cout, T)).add(resid, bct(cout, T));
     cc.epi = epi;
-    cc.resid = resid;
-    cc.rb = (long)cout * T;
-    cc.rc = T;
-    cc.rt = 1;
     run_conv(L, cc, s);
   };
   if (G.tdsep || G.tfm) {
@@ -414,20 +386,13 @@ void glow_encode(tts_ctx* c, const int64_t* d_ids, const int32_t* h_lens, const 
   // DurationPredictor (duration_predictor.py:29-40): conv -> relu -> LN, twice, then proj; the
   // input is [x; g] with g constant over time (encoder.py:131-135), masked like x by the conv
   if (G.c_pad > 0) {
-    ConvCall cc;
-    cc.lens = dl;
-    cc.B = B;
-    cc.max_q = T;
-    cc.nsrc = 2;
-    cc.s[0] = src_of(x, (long)H * T, T, 1, H, 0);
-    cc.s[1] = src_of(W.g.f(), G.c_pad, 1, 0, G.c_pad, 0);
-    cc.out = W.hdp.f();
-    cc.ob = (long)F * T;
-    cc.oc = T;
-    cc.ot = 1;
+    // g: one vector per row, broadcast over time by a time stride of 0
+    ConvCall cc = conv_call(c, dl, B, T).in(x, bct(H, T), H).in2(W.g.f(), Layout{G.c_pad, 1, 0}, G.c_pad);
+    cc.to(W.hdp.f(), bct(F, T));
     cc.epi = 1;
-    // two sources: the fp32 conv (conv_x3 stages one source; this k3 conv over ~T x (H + c_pad)
-    // inputs is a few microseconds of the call either way)
+    // two sources: the fp32 conv, no range flag (conv_x3 stages one source; this k3 conv over
+    // ~T x (H + c_pad) inputs is a few microseconds of the call either way)
+    cc.oflow = nullptr;
     run_conv(G.dp1, cc, s);
   } else {
     conv(G.dp1, x, H, W.hdp.f(), F, 1);
@@ -441,7 +406,6 @@ void glow_encode(tts_ctx* c, const int64_t* d_ids, const int32_t* h_lens, const 
   HIP_OK(hipStreamSynchronize(s));
   int mx = 1;
   W.h_ylens.assign(h_ylens, h_ylens + B);
-  W.h_klens.resize(B);
   for (int b = 0; b < B; ++b) mx = std::max(mx, (int)h_ylens[b]);
   W.Ty = mx;
 }
@@ -456,20 +420,8 @@ struct FlowConvs {
   void conv(const ConvLayer& L, const float* in, int in_rows, float* out, int out_rows, const float* resid, int epi,
             int resid_rows = 0, const float* aux = nullptr) const {
     const auto& G = c->glow;
-    ConvCall cc;
-    cc.lens = kl;
-    cc.B = B;
-    cc.oflow = x3_flag(c);
-    cc.max_q = K;
-    cc.s[0] = src_of(in, (long)in_rows * K, K, 1, L.Cin, 0);
-    cc.out = out;
-    cc.ob = (long)out_rows * K;
-    cc.oc = K;
-    cc.ot = 1;
-    cc.resid = resid;
-    cc.rb = (long)out_rows * K;
-    cc.rc = K;
-    cc.rt = 1;
+    ConvCall cc = conv_call(c, kl, B, K).in(in, bct(in_rows, K), L.Cin).to(out, bct(out_rows, K));
+    cc.add(resid, bct(out_rows, K));
     cc.epi = epi;
     cc.resid_rows = resid_rows;
     cc.aux = aux;
@@ -505,23 +457,21 @@ void glow_decode(tts_ctx* c, const float* d_noise, float noise_scale, int Ty, fl
   TTS_CHECK(W.B > 0 && Ty == W.Ty, "glow: decode after encode with Ty = max(y_lengths)");
   hipStream_t s = c->s;
   const int B = W.B, Tx = W.Tx, H = G.H, C = G.C, C2 = 2 * C, K = Ty / 2;
-  long gen = 0;
   const int K1 = std::max(K, 1);
-  grow<float>(W.z, (size_t)B * C * Ty, gen);
-  grow<float>(W.sq, (size_t)B * C2 * K1, gen);
-  grow<float>(W.sq2, (size_t)B * C2 * K1, gen);
-  grow<float>(W.whs, (size_t)B * 2 * H * K1, gen);
-  grow<float>(W.wacts, (size_t)B * H * K1, gen);
+  ensure<float>(W.z, (size_t)B * C * Ty);
+  ensure<float>(W.sq, (size_t)B * C2 * K1);
+  ensure<float>(W.sq2, (size_t)B * C2 * K1);
+  ensure<float>(W.whs, (size_t)B * 2 * H * K1);
+  ensure<float>(W.wacts, (size_t)B * H * K1);
   launch_glow_expand(W.om.f(), C, Tx, W.lens.i(), W.cum.f(), W.ylens.i(), Ty, d_noise, noise_scale, d_ymean, W.z.f(),
                      d_attn, B, s);
   HIP_OK(hipMemcpyAsync(d_logw, W.logw.p, (size_t)B * Tx * 4, hipMemcpyDeviceToDevice, s));
   HIP_OK(hipMemsetAsync(d_y, 0, (size_t)B * C * 2 * K * 4, s));
   if (K == 0) return;
-  // squeezed lengths floor(y_len / 2) (decoder.py:13-15); the staging vector lives in the
-  // workspace so the async copy never reads a dead host buffer
-  for (int b = 0; b < B; ++b) W.h_klens[b] = W.h_ylens[b] / 2;
-  HIP_OK(hipMemcpyAsync(W.klens.p, W.h_klens.data(), B * 4, hipMemcpyHostToDevice, s));
-  const int* kl = W.klens.i();
+  // squeezed lengths floor(y_len / 2) (decoder.py:13-15)
+  RowInts hk{};
+  for (int b = 0; b < B; ++b) hk.v[b] = W.h_ylens[b] / 2;
+  const int* kl = put_rows(W.klens, hk.v, B, s);
   launch_glow_squeeze(W.z.f(), C, Ty, W.ylens.i(), W.sq.f(), K, B, s);
   const FlowConvs fc{c, kl, B, K};
   float* x = W.sq.f();
@@ -541,9 +491,8 @@ void glow_decode(tts_ctx* c, const float* d_noise, float noise_scale, int Ty, fl
 // lengths on the device (xl, yl) -> W.xof (B, Ty)
 void glow_search(tts_ctx* c, const float* d_logp, const int* xl, const int* yl, int max_xlen, int B, int Tx, int Ty) {
   auto& W = c->glws;
-  long gen = 0;
-  grow<unsigned long long>(W.masbits, (size_t)B * glow_mas_bits_words(Tx, Ty), gen);
-  grow<int>(W.xof, (size_t)B * Ty, gen);
+  ensure<unsigned long long>(W.masbits, (size_t)B * glow_mas_bits_words(Tx, Ty));
+  ensure<int>(W.xof, (size_t)B * Ty);
   launch_glow_mas(d_logp, Tx, Ty, xl, yl, max_xlen, static_cast<unsigned long long*>(W.masbits.p), W.xof.i(), B, c->s);
 }
 
@@ -559,8 +508,7 @@ void glow_align(tts_ctx* c, const float* d_y, const int32_t* h_ylens, int Ty, fl
   TTS_CHECK(W.B > 0, "glow: align after encode of the same batch");
   const int B = W.B, Tx = W.Tx, H = G.H, C = G.C, C2 = 2 * C, K = Ty / 2, Te = 2 * K;
   TTS_CHECK(Ty >= 2, "glow align: the mel needs at least 2 frames");
-  W.h_aylens.resize(B);
-  W.h_aklens.resize(B);
+  RowInts ye2{}, ke{};  // even mel lengths and their halves
   TTS_CHECK((int)W.h_xlens.size() == B, "glow: align after encode of the same batch");
   int max_xlen = 1;
   for (int b = 0; b < B; ++b) {
@@ -570,29 +518,26 @@ void glow_align(tts_ctx* c, const float* d_y, const int32_t* h_ylens, int Ty, fl
     TTS_CHECK(ye >= 2 && ye >= xl, "glow align: row " + std::to_string(b) + " has " + std::to_string(ye) +
                                        " mel frames (rounded down to even) for " + std::to_string(xl) +
                                        " tokens; the alignment needs at least max(2, tokens)");
-    W.h_aylens[b] = ye;
-    W.h_aklens[b] = ye / 2;
+    ye2.v[b] = ye;
+    ke.v[b] = ye / 2;
     max_xlen = std::max(max_xlen, xl);
   }
   hipStream_t s = c->s;
   const int tiles = (K + 63) / 64;
-  long gen = 0;
-  grow<int>(W.aylens, 64, gen);
-  grow<int>(W.aklens, 64, gen);
-  grow<float>(W.sq, (size_t)B * C2 * K, gen);
-  grow<float>(W.sq2, (size_t)B * C2 * K, gen);
-  grow<float>(W.eo, (size_t)B * C2 * K, gen);
-  grow<float>(W.whs, (size_t)B * 2 * H * K, gen);
-  grow<float>(W.wacts, (size_t)B * H * K, gen);
-  grow<double>(W.ldpart, (size_t)G.flows * B * tiles, gen);
+  ensure<int>(W.aylens, 64);
+  ensure<int>(W.aklens, 64);
+  ensure<float>(W.sq, (size_t)B * C2 * K);
+  ensure<float>(W.sq2, (size_t)B * C2 * K);
+  ensure<float>(W.eo, (size_t)B * C2 * K);
+  ensure<float>(W.whs, (size_t)B * 2 * H * K);
+  ensure<float>(W.wacts, (size_t)B * H * K);
+  ensure<double>(W.ldpart, (size_t)G.flows * B * tiles);
   if (!d_logp) {
-    grow<float>(W.logp, (size_t)B * Tx * Te, gen);
+    ensure<float>(W.logp, (size_t)B * Tx * Te);
     d_logp = W.logp.f();
   }
-  HIP_OK(hipMemcpyAsync(W.aylens.p, W.h_aylens.data(), B * 4, hipMemcpyHostToDevice, s));
-  HIP_OK(hipMemcpyAsync(W.aklens.p, W.h_aklens.data(), B * 4, hipMemcpyHostToDevice, s));
-  const int* yl = W.aylens.i();
-  const int* kl = W.aklens.i();
+  const int* yl = put_rows(W.aylens, ye2.v, B, s);
+  const int* kl = put_rows(W.aklens, ke.v, B, s);
   launch_glow_squeeze(d_y, C, Ty, yl, W.sq.f(), K, B, s);
   const FlowConvs fc{c, kl, B, K};
   float* x = W.sq.f();
@@ -623,22 +568,19 @@ void glow_mas(tts_ctx* c, const float* d_logp, const int32_t* h_xlens, const int
               float* d_path) {
   auto& W = c->glws;
   TTS_CHECK(B >= 1 && B <= 64 && Tx >= 1 && Tx <= 4096 && Ty >= 1, "glow mas: bad sizes");
-  W.h_mxl.assign(h_xlens, h_xlens + B);  // staging vectors live in the workspace, as in glow_decode
-  W.h_myl.assign(h_ylens, h_ylens + B);
   int max_xlen = 1;
   for (int b = 0; b < B; ++b) {
-    const int xl = W.h_mxl[b], yl = W.h_myl[b];
+    const int xl = h_xlens[b], yl = h_ylens[b];
     TTS_CHECK(xl >= 1 && xl <= Tx && yl >= 1 && yl <= Ty, "glow mas: lengths out of range");
     // below that the reference's search reads outside its band (core.pyx:18-35)
     TTS_CHECK(yl >= xl, "glow mas: row " + std::to_string(b) + " has fewer frames than tokens");
     max_xlen = std::max(max_xlen, xl);
   }
-  long gen = 0;
-  grow<int>(W.mxl, 64, gen);
-  grow<int>(W.myl, 64, gen);
-  HIP_OK(hipMemcpyAsync(W.mxl.p, W.h_mxl.data(), B * 4, hipMemcpyHostToDevice, c->s));
-  HIP_OK(hipMemcpyAsync(W.myl.p, W.h_myl.data(), B * 4, hipMemcpyHostToDevice, c->s));
-  glow_search(c, d_logp, W.mxl.i(), W.myl.i(), max_xlen, B, Tx, Ty);
+  ensure<int>(W.mxl, 64);
+  ensure<int>(W.myl, 64);
+  const int* xl = put_rows(W.mxl, h_xlens, B, c->s);
+  const int* yl = put_rows(W.myl, h_ylens, B, c->s);
+  glow_search(c, d_logp, xl, yl, max_xlen, B, Tx, Ty);
   launch_glow_path(W.xof.i(), Tx, Ty, d_path, B, c->s);
   HIP_OK(hipStreamSynchronize(c->s));
 }

@@ -112,11 +112,8 @@ int tts_taco_style_mel(tts_ctx* c, const float* d_mel, const int32_t* h_lens, in
     TTS_CHECK(B >= 1 && B <= BMAX, "B must be in [1, 64]");
     TTS_CHECK(N_max >= 1 && N_max <= (1 << 16), "N_max must be in [1, 65536]");
     TTS_CHECK(!M.gst_es_q || d_spk_emb, "this model's style query takes the speaker embeddings: pass them");
-    GstLens lens{};
-    for (int b = 0; b < B; ++b) {
-      TTS_CHECK(h_lens[b] >= 1 && h_lens[b] <= N_max, "style mel lens out of range");
-      lens.v[b] = h_lens[b];
-    }
+    check_rows(h_lens, B, 1, N_max, "style mel lens out of range");
+    const RowInts lens = row_ints(h_lens, B);
     DeviceGuard g(c->device);
     // layer 1's output (B, W1, 40, 32) and layer 2's (B, W2, 20, 32); the later, smaller layers alternate
     const int W1 = (N_max + 1) / 2, W2 = (W1 + 1) / 2;

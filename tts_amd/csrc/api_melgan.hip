@@ -135,18 +135,48 @@ static void melgan_finalize(tts_ctx* c, int in_ch, int out_ch, int base, const i
   G.ready = true;
 }
 
-int ttsh::run_generator(tts_ctx* c, const VocCall& v, float* out, GenTail* tail) {
+namespace {
+
+// One generator run: the call, where its lengths and range flag are, and the running activation
+// x (B, C, Ls) at mul positions per mel frame (xo: the other ping-pong buffer)
+struct GenRun {
+  tts_ctx* c;
+  const VocCall& v;
+  hipStream_t s;
+  const int* lens;  // device lengths (mel frames); v.h_lens: the same on the host, or per-row upper bounds
+  unsigned* oflow;  // range flag: the split-f16 kernels run; null: fp32
+  int Lb, pad;      // the longest row's padded mel frames, inference padding
+  float *x, *xo;
+  int C, mul;
+  long Ls;
+  // a conv of this run over max_q positions, on the run's own range flag
+  ConvCall conv(int max_q) const {
+    ConvCall cc;
+    cc.lens = lens;
+    cc.B = v.B;
+    cc.max_q = max_q;
+    cc.oflow = oflow;
+    cc.len_add = 2 * pad;
+    return cc;
+  }
+  void wrote(int C_, long Ls_, int mul_) {  // a step wrote the next activation into xo
+    std::swap(x, xo);
+    C = C_;
+    Ls = Ls_;
+    mul = mul_;
+  }
+};
+
+// argument checks, workspace, lengths on the device
+GenRun gen_begin(tts_ctx* c, const VocCall& v) {
   auto& G = c->mg;
   auto& W = c->mws;
-  const float* mel = v.mel;
-  const int64_t* mel_strides = v.mel_strides;
   const int32_t* h_lens = v.h_lens;
   const int B = v.B, M_max = v.M_max, pad = v.pad;
-  const bool dev_lens = v.dev_lens;
   hipStream_t s = v.s ? v.s : c->s;
   TTS_CHECK(G.ready, "melgan weights not finalized");
   TTS_CHECK(B >= 1, "B >= 1");
-  for (int b = 0; b < B && !dev_lens; ++b) {
+  for (int b = 0; b < B && !v.dev_lens; ++b) {
     TTS_CHECK(h_lens[b] >= 1 && h_lens[b] <= M_max, "mel lens out of range");
     TTS_CHECK(h_lens[b] + 2 * pad >= 4, "ReflectionPad1d(3): mel frames + 2*padding must be >= 4");
     for (int k = 0; k < G.nres && !G.ups.empty(); ++k)  // ResidualStack ReflectionPad1d(dilation), stage 0
@@ -154,8 +184,6 @@ int ttsh::run_generator(tts_ctx* c, const VocCall& v, float* out, GenTail* tail)
                 "ReflectionPad1d: a residual stack's dilation must be < the first stage's length");
   }
   const int Lb = M_max + 2 * pad;
-  int up = 1;
-  for (int u : G.ups) up *= u;
   size_t maxelems = (size_t)G.base * Lb;
   {
     int mul = 1, Cc = G.base;
@@ -173,175 +201,168 @@ int ttsh::run_generator(tts_ctx* c, const VocCall& v, float* out, GenTail* tail)
   }
   W.xa.ensure((size_t)B * maxelems * 4);
   W.xb.ensure((size_t)B * maxelems * 4);
-  std::vector<int> lens(h_lens, h_lens + B);
-  if (!dev_lens) HIP_OK(hipMemcpyAsync(vld, lens.data(), B * 4, hipMemcpyHostToDevice, s));
+  if (!v.dev_lens) put_rows(vld, h_lens, B, s);
   else TTS_CHECK(v.d_lens || W.lens.bytes >= (size_t)B * 4, "vocoder lengths buffer");
-  ConvCall cc;
-  cc.lens = vld;
-  cc.B = B;
-  cc.oflow = c->gemm_x3 && v.flag ? v.flag : x3_flag(c);
-  cc.len_add = 2 * pad;
-  // layers[0..1]: replicate pad (inference_padding) + ReflectionPad1d(3) + Conv1d(k7)
-  if (mel_strides) {
-    TTS_CHECK(mel_strides[1] >= 1 && mel_strides[2] >= 1 && mel_strides[1] < (1L << 31) && mel_strides[2] < (1L << 31) &&
-                  (mel_strides[0] >= 1 || B == 1) && mel_strides[0] >= 0,
+  unsigned* oflow = c->gemm_x3 && v.flag ? v.flag : x3_flag(c);
+  // no activation yet: the input conv writes xo = W.xa
+  return GenRun{c, v, s, vld, oflow, Lb, pad, W.xb.f(), W.xa.f(), 0, 1, 0};
+}
+
+// layers[0..1]: replicate pad (inference_padding) + ReflectionPad1d(3) + Conv1d(k7) on the mel
+void gen_input_conv(GenRun& r) {
+  const auto& G = r.c->mg;
+  const VocCall& v = r.v;
+  ConvCall cc = r.conv(r.Lb);
+  if (const int64_t* st = v.mel_strides) {
+    TTS_CHECK(st[1] >= 1 && st[2] >= 1 && st[1] < (1L << 31) && st[2] < (1L << 31) && (st[0] >= 1 || v.B == 1) &&
+                  st[0] >= 0,
               "mel strides must be positive");
-    TTS_CHECK(mel_strides[1] != 1 || (mel_strides[2] % 4 == 0 && (reinterpret_cast<uintptr_t>(mel) & 15) == 0),
+    TTS_CHECK(st[1] != 1 || (st[2] % 4 == 0 && (reinterpret_cast<uintptr_t>(v.mel) & 15) == 0),
               "channel stride 1 needs a frame stride divisible by 4 and a 16-byte aligned mel");
-    cc.s[0] = src_of(mel, (long)mel_strides[0], (int)mel_strides[1], (int)mel_strides[2], G.in_ch, 0);
+    cc.in(v.mel, Layout{(long)st[0], (int)st[1], (int)st[2]}, G.in_ch);
   } else {
-    cc.s[0] = src_of(mel, (long)G.in_ch * M_max, M_max, 1, G.in_ch, 0);
+    cc.in(v.mel, bct(G.in_ch, v.M_max), G.in_ch);
   }
   cc.pad_mode = 1;
-  cc.rep_pad = pad;
-  cc.in_mul = cc.q_mul = 1;
-  cc.max_q = Lb;
-  float* x = W.xa.f();
-  float* xo = W.xb.f();
-  int C = G.base, mul = 1;
-  long Ls = Lb;
-  cc.out = x;
-  cc.ob = (long)C * Ls;
-  cc.oc = Ls;
-  cc.ot = 1;
-  run_conv(G.conv_in, cc, s);
-  cc.rep_pad = 0;
-  // blocks 0-2 of stage i as one resstack_x3 launch (x: the stage input; with ct, x is the
-  // ConvTranspose input and the kernel computes the stage input per tile): false if not covered
-  auto stack3 = [&](size_t i, int Cs, long Lss, int muls, const float* xs, float* ys, const ConvLayer* ct,
-                    const float* xin, int Cin, long Lin) {
-    if (!(cc.oflow && G.nres >= 3 && sw::stack_fuse() && G.rb_wd16[i * G.nres].p)) return false;
-    if (Cs == 96 && !sw::stack_fuse96()) return false;
-    int dil[3];
-    for (int k = 0; k < 3; ++k) dil[k] = G.dconv[i * G.nres + k].dil;
-    if (!resstack_x3_supported(Cs, dil, 3)) return false;
-    StackArgs sa{};
-    sa.B = B;
-    sa.x = xs;
-    sa.y = ys;
-    sa.sb = (long)Cs * Lss;
-    sa.Ls = (int)Lss;
-    sa.lens = vld;
-    sa.len_add = 2 * pad;
-    sa.mul = muls;
-    for (int k = 0; k < 3; ++k) {
-      sa.dil[k] = dil[k];
-      sa.wd16[k] = Cs % 32 == 16 ? G.rb_wd16p[i * G.nres + k].p : G.rb_wd16[i * G.nres + k].p;
-      sa.wf16[k] = G.rb_wf16[i * G.nres + k].p;
-      sa.bd[k] = G.dconv[i * G.nres + k].bias.f();
-      sa.bf[k] = G.fused[i * G.nres + k].bias.f();
-    }
-    sa.oflow = cc.oflow;
-    if (ct) {
-      sa.xin = xin;
-      sa.sb_in = (long)Cin * Lin;
-      sa.Ls_in = (int)Lin;
-      sa.ct16 = ct->W16.p;
-      sa.ct_bias = ct->bias.f();
-    }
-    if (!resstack_x3_fits(sa, lens.data())) return false;
-    launch_resstack_x3(sa, lens.data(), Cs, s);
-    return true;
-  };
-  for (size_t i = 0; i < G.ups.size(); ++i) {
-    const int u = G.ups[i];
-    int bk0 = 0;
-    if (u == 2 && C == 96 && sw::ct_fuse() && cc.oflow && G.convTm[i].W16.p &&
-        stack3(i, C / 2, Ls * u, mul * u, nullptr, xo, &G.convTm[i], x, C, Ls)) {
-      // LeakyReLU + ConvTranspose1d + blocks 0-2 in one launch (resstack_x3.hip CTU = 2)
-      std::swap(x, xo);
-      C /= 2;
-      Ls *= u;
-      mul *= u;
-      bk0 = 3;
-    }
-    // LeakyReLU + ConvTranspose1d as u polyphase 2-tap convs
-    ConvCall t = cc;
-    t.s[0] = src_of(x, (long)C * Ls, Ls, 1, C, 1);
-    t.pad_mode = 0;
-    t.in_mul = t.q_mul = mul;
-    t.max_q = Lb * mul;
-    t.out_mul = u;
-    const int Cn = C / 2;
-    const long Ln = Ls * u;
-    t.out = xo;
-    t.ob = (long)Cn * Ln;
-    t.oc = Ln;
-    t.ot = 1;
-    if (bk0 == 0) {
-      if (t.oflow && G.convTm[i].W16.p) {  // all u phases as one GEMM over input positions 0 .. L
-        t.out_mul = 1;
-        t.max_q = Lb * mul + 1;
-        t.merged_u = u;
-        run_conv(G.convTm[i], t, s);
-      } else {
-        run_conv(G.convT[i], t, s);
-      }
-      std::swap(x, xo);
-      C = Cn;
-      Ls = Ln;
-      mul *= u;
-      // blocks 0-2 in one pass over the stage (resstack_x3.hip)
-      if (stack3(i, C, Ls, mul, x, xo, nullptr, nullptr, 0, 0)) {
-        std::swap(x, xo);
-        bk0 = 3;
-      }
-    }
-    for (int bk = bk0; bk < G.nres; ++bk) {  // fused ResidualStack blocks (resblock.hip)
-      const ConvLayer& dl = G.dconv[i * G.nres + bk];
-      const ConvLayer& fl = G.fused[i * G.nres + bk];
-      ResArgs ra{};
-      ra.x = x;
-      ra.y = xo;
-      ra.sb = (long)C * Ls;
-      ra.Ls = (int)Ls;
-      ra.lens = vld;
-      ra.len_add = 2 * pad;
-      ra.mul = mul;
-      ra.dil = dl.dil;
-      ra.Wd = dl.W.f();
-      ra.bd = dl.bias.f();
-      ra.Wf = fl.W.f();
-      ra.bf = fl.bias.f();
-      ra.max_q = Lb * mul;
-      ra.B = B;
-      const DevBuf& w16 = G.rb_wd16[i * G.nres + bk];
-      if (cc.oflow && w16.p) {
-        ra.Wd16 = w16.p;
-        ra.Wf16 = G.rb_wf16[i * G.nres + bk].p;
-        ra.oflow = cc.oflow;
-        launch_resblock_x3(ra, lens.data(), C, s);
-      } else {
-        launch_resblock(ra, C, s);
-      }
-      std::swap(x, xo);
-    }
+  cc.rep_pad = r.pad;
+  cc.to(r.xo, bct(G.base, r.Lb));
+  run_conv(G.conv_in, cc, r.s);
+  r.wrote(G.base, r.Lb, 1);
+}
+
+// LeakyReLU + ConvTranspose1d of stage i: all u phases as one GEMM over input positions 0 .. L
+// (split-f16, phase-merged weights), or u polyphase 2-tap convs
+void gen_conv_transpose(GenRun& r, size_t i) {
+  const auto& G = r.c->mg;
+  const int u = G.ups[i], Cn = r.C / 2;
+  const long Ln = r.Ls * u;
+  const bool merged = r.oflow && G.convTm[i].W16.p;
+  ConvCall t = r.conv(merged ? r.Lb * r.mul + 1 : r.Lb * r.mul);
+  t.in(r.x, bct(r.C, r.Ls), r.C, 1).to(r.xo, bct(Cn, Ln));
+  t.in_mul = t.q_mul = r.mul;
+  t.out_mul = merged ? 1 : u;
+  t.merged_u = merged ? u : 0;
+  run_conv(merged ? G.convTm[i] : G.convT[i], t, r.s);
+  r.wrote(Cn, Ln, r.mul * u);
+}
+
+// Blocks 0-2 of stage i as one resstack_x3 launch, over the stage's input x; with_ct: x is the
+// ConvTranspose's input and the kernel computes the stage's input per tile (LeakyReLU +
+// ConvTranspose1d + blocks 0-2, resstack_x3.hip CTU = 2). False, and nothing launched, if not covered.
+bool gen_stack(GenRun& r, size_t i, bool with_ct) {
+  const auto& G = r.c->mg;
+  const int u = G.ups[i];
+  if (with_ct && !(u == 2 && r.C == 96 && sw::ct_fuse() && r.oflow && G.convTm[i].W16.p)) return false;
+  const int Cs = with_ct ? r.C / 2 : r.C, muls = with_ct ? r.mul * u : r.mul;
+  const long Lss = with_ct ? r.Ls * u : r.Ls;
+  if (!(r.oflow && G.nres >= 3 && sw::stack_fuse() && G.rb_wd16[i * G.nres].p)) return false;
+  if (Cs == 96 && !sw::stack_fuse96()) return false;
+  int dil[3];
+  for (int k = 0; k < 3; ++k) dil[k] = G.dconv[i * G.nres + k].dil;
+  if (!resstack_x3_supported(Cs, dil, 3)) return false;
+  StackArgs sa{};
+  sa.B = r.v.B;
+  sa.x = with_ct ? nullptr : r.x;
+  sa.y = r.xo;
+  sa.sb = (long)Cs * Lss;
+  sa.Ls = (int)Lss;
+  sa.lens = r.lens;
+  sa.len_add = 2 * r.pad;
+  sa.mul = muls;
+  for (int k = 0; k < 3; ++k) {
+    sa.dil[k] = dil[k];
+    sa.wd16[k] = Cs % 32 == 16 ? G.rb_wd16p[i * G.nres + k].p : G.rb_wd16[i * G.nres + k].p;
+    sa.wf16[k] = G.rb_wf16[i * G.nres + k].p;
+    sa.bd[k] = G.dconv[i * G.nres + k].bias.f();
+    sa.bf[k] = G.fused[i * G.nres + k].bias.f();
   }
-  if (tail) {
-    tail->x = x;
-    tail->C = C;
-    tail->Ls = Ls;
-    tail->mul = mul;
-    return up;
+  sa.oflow = r.oflow;
+  if (with_ct) {
+    sa.xin = r.x;
+    sa.sb_in = (long)r.C * r.Ls;
+    sa.Ls_in = (int)r.Ls;
+    sa.ct16 = G.convTm[i].W16.p;
+    sa.ct_bias = G.convTm[i].bias.f();
   }
+  if (!resstack_x3_fits(sa, r.v.h_lens)) return false;
+  launch_resstack_x3(sa, r.v.h_lens, Cs, r.s);
+  r.wrote(Cs, Lss, muls);
+  return true;
+}
+
+// one fused ResidualStack block (resblock_x3.hip split-f16, or resblock.hip fp32)
+void gen_block(GenRun& r, size_t i, int bk) {
+  const auto& G = r.c->mg;
+  const ConvLayer& dl = G.dconv[i * G.nres + bk];
+  const ConvLayer& fl = G.fused[i * G.nres + bk];
+  ResArgs ra{};
+  ra.x = r.x;
+  ra.y = r.xo;
+  ra.sb = (long)r.C * r.Ls;
+  ra.Ls = (int)r.Ls;
+  ra.lens = r.lens;
+  ra.len_add = 2 * r.pad;
+  ra.mul = r.mul;
+  ra.dil = dl.dil;
+  ra.Wd = dl.W.f();
+  ra.bd = dl.bias.f();
+  ra.Wf = fl.W.f();
+  ra.bf = fl.bias.f();
+  ra.max_q = r.Lb * r.mul;
+  ra.B = r.v.B;
+  const DevBuf& w16 = G.rb_wd16[i * G.nres + bk];
+  if (r.oflow && w16.p) {
+    ra.Wd16 = w16.p;
+    ra.Wf16 = G.rb_wf16[i * G.nres + bk].p;
+    ra.oflow = r.oflow;
+    launch_resblock_x3(ra, r.v.h_lens, r.C, r.s);
+  } else {
+    launch_resblock(ra, r.C, r.s);
+  }
+  r.wrote(r.C, r.Ls, r.mul);
+}
+
+// LeakyReLU + ReflectionPad1d(3) + Conv1d(k7) + tanh into out (B, out_ch, Ls), rows zero past their length
+void gen_output_conv(GenRun& r, float* out) {
+  const auto& G = r.c->mg;
+  const int B = r.v.B;
   if (G.out_ch == 1) {  // full-band output stage on the VALU (melgan_out.hip)
-    HIP_OK(hipMemsetAsync(out, 0, (size_t)B * Ls * 4, s));
-    launch_out_conv1(x, (long)C * Ls, Ls, C, G.out_w.f(), G.out_b.f(), vld, 2 * pad, mul, (int)(Lb * mul), B,
-                     out, Ls, s);
-    return up;
+    HIP_OK(hipMemsetAsync(out, 0, (size_t)B * r.Ls * 4, r.s));
+    launch_out_conv1(r.x, (long)r.C * r.Ls, r.Ls, r.C, G.out_w.f(), G.out_b.f(), r.lens, 2 * r.pad, r.mul,
+                     (int)(r.Lb * r.mul), B, out, r.Ls, r.s);
+    return;
   }
-  ConvCall o = cc;
-  o.s[0] = src_of(x, (long)C * Ls, Ls, 1, C, 1);
+  ConvCall o = r.conv(r.Lb * r.mul);
+  o.in(r.x, bct(r.C, r.Ls), r.C, 1).to(out, bct(G.out_ch, r.Ls));
   o.pad_mode = 1;
-  o.in_mul = o.q_mul = mul;
-  o.max_q = Lb * mul;
+  o.in_mul = o.q_mul = r.mul;
   o.epi = 2;
-  o.out = out;
-  o.ob = (long)G.out_ch * Ls;
-  o.oc = Ls;
-  o.ot = 1;
-  HIP_OK(hipMemsetAsync(out, 0, (size_t)B * G.out_ch * Ls * 4, s));
-  run_conv(G.conv_out, o, s);
+  HIP_OK(hipMemsetAsync(out, 0, (size_t)B * G.out_ch * r.Ls * 4, r.s));
+  run_conv(G.conv_out, o, r.s);
+}
+
+}  // namespace
+
+int ttsh::run_generator(tts_ctx* c, const VocCall& v, float* out, GenTail* tail) {
+  GenRun r = gen_begin(c, v);
+  const auto& G = c->mg;
+  gen_input_conv(r);
+  int up = 1;
+  for (size_t i = 0; i < G.ups.size(); ++i) {
+    up *= G.ups[i];
+    // ConvTranspose and blocks 0-2 in one launch; else the ConvTranspose, then blocks 0-2 in one
+    // launch; the blocks neither covers run one by one
+    int bk = 0;
+    if (gen_stack(r, i, /*with_ct=*/true)) {
+      bk = 3;
+    } else {
+      gen_conv_transpose(r, i);
+      if (gen_stack(r, i, /*with_ct=*/false)) bk = 3;
+    }
+    for (; bk < G.nres; ++bk) gen_block(r, i, bk);
+  }
+  if (tail) *tail = GenTail{r.x, r.C, r.Ls, r.mul};  // the fused output conv + PQMF kernel takes it from here
+  else gen_output_conv(r, out);
   return up;
 }
 
@@ -437,10 +458,8 @@ int tts_pqmf_synthesis(tts_ctx* c, const float* d_x, int B, int N, int L, const 
     TTS_CHECK(B >= 1 && N >= 1 && N <= 8 && L >= 1 && taps >= 0, "bad sizes");
     DeviceGuard g(c->device);
     enter(c, stream);
-    std::vector<int> lens(B, L);
-    c->mws.lens.ensure(B * 4);
-    HIP_OK(hipMemcpyAsync(c->mws.lens.p, lens.data(), B * 4, hipMemcpyHostToDevice, c->s));
-    launch_pqmf_synthesis(d_x, (long)N * L, L, d_G, N, taps, c->mws.lens.i(), 0, 1, L, B, d_y, (long)N * L, c->s);
+    const int* dl = fill_rows(c->mws.lens, L, B, c->s);
+    launch_pqmf_synthesis(d_x, (long)N * L, L, d_G, N, taps, dl, 0, 1, L, B, d_y, (long)N * L, c->s);
     HIP_OK(hipStreamSynchronize(c->s));
     leave(c, stream);
   });

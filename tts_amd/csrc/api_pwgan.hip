@@ -102,36 +102,24 @@ void pwgan_infer(tts_ctx* c, const float* mel, const int32_t* h_lens, int B, int
   auto& W = c->pws;
   TTS_CHECK(P.ready, "pwgan weights not finalized");
   TTS_CHECK(B >= 1 && M_max >= 1 && pad >= 0 && pad <= 64, "pwgan: bad sizes");
-  for (int b = 0; b < B; ++b) TTS_CHECK(h_lens[b] >= 1 && h_lens[b] <= M_max, "pwgan: mel lens out of range");
+  check_rows(h_lens, B, 1, M_max, "pwgan: mel lens out of range");
   hipStream_t s = c->s;
   int hop = 1;
   for (int u : P.ups) hop *= u;
   const int Lf = M_max + 2 * pad, Tmax = Lf * hop;
-  W.lens.ensure(B * 4);
   W.ca.ensure((size_t)B * 80 * Tmax * 4);
   W.cb.ensure((size_t)B * 80 * Tmax * 4);
   W.xa.ensure((size_t)B * 64 * Tmax * 4);
   W.xb.ensure((size_t)B * 64 * Tmax * 4);
   W.skip.ensure((size_t)B * 64 * Tmax * 4);
-  std::vector<int> lens(h_lens, h_lens + B);
-  HIP_OK(hipMemcpyAsync(W.lens.p, lens.data(), B * 4, hipMemcpyHostToDevice, s));
-  const int* dl = W.lens.i();
+  const int* dl = put_rows(W.lens, h_lens, B, s);
   // replicate pad + ConvUpsample.conv_in (1x1, frame rate)
-  ConvCall cc;
-  cc.lens = dl;
-  cc.B = B;
-  cc.len_add = 2 * pad;
-  cc.s[0] = src_of(mel, (long)80 * M_max, M_max, 1, 80, 0);
-  cc.oflow = x3_flag(c);
-  cc.pad_mode = 2;
-  cc.rep_pad = pad;
-  cc.max_q = Lf;
   float* cin = W.cb.f();
   float* cout = W.ca.f();
-  cc.out = cin;
-  cc.ob = (long)80 * Lf;
-  cc.oc = Lf;
-  cc.ot = 1;
+  ConvCall cc = conv_call(c, dl, B, Lf).in(mel, bct(80, M_max), 80).to(cin, bct(80, Lf));
+  cc.len_add = 2 * pad;
+  cc.pad_mode = 2;
+  cc.rep_pad = pad;
   run_conv(P.conv_in, cc, s);
   int L = Lf, mul = 1;
   for (size_t i = 0; i < P.ups.size(); ++i) {

@@ -89,32 +89,17 @@ void run_encoder(tts_ctx* c, const int64_t* ids, int B, int T_max, float* enc_ou
   auto& W = c->tws;
   const int* lens = W.lens.i();
   launch_embed_gather(ids, T_max, M.emb.f(), M.num_chars, 512, lens, B, W.x0.f(), s, rowmap);
-  ConvCall cc;
-  cc.lens = lens;
-  cc.B = B;
-  cc.oflow = x3_flag(c);
-  cc.max_q = T_max;
-  cc.pad_mode = 0;
-  cc.epi = 1;
-  cc.s[0] = src_of(W.x0.f(), (long)T_max * 512, 1, 512, 512, 0);
-  cc.out = W.ca.f();
-  cc.ob = (long)512 * T_max;
-  cc.oc = T_max;
-  cc.ot = 1;
-  run_conv(M.enc[0], cc, s);
-  cc.s[0] = src_of(W.ca.f(), (long)512 * T_max, T_max, 1, 512, 0);
-  cc.out = W.cb.f();
-  run_conv(M.enc[1], cc, s);
-  cc.s[0] = src_of(W.cb.f(), (long)512 * T_max, T_max, 1, 512, 0);
-  cc.out = W.ca.f();
-  run_conv(M.enc[2], cc, s);
-  cc.s[0] = src_of(W.ca.f(), (long)512 * T_max, T_max, 1, 512, 0);
-  cc.out = W.gin.f();  // (B, T_max, 2048): time-major, so one step's gates of a tile are contiguous
-  cc.ob = (long)2048 * T_max;
-  cc.oc = 1;
-  cc.ot = 2048;
-  cc.epi = 0;
-  run_conv(M.lstm_in, cc, s);
+  const Layout x512 = bct(512, T_max);
+  auto conv = [&](const ConvLayer& L, const float* in, Layout li, float* out, Layout lo, int epi) {
+    ConvCall cc = conv_call(c, lens, B, T_max).in(in, li, 512).to(out, lo);
+    cc.epi = epi;
+    run_conv(L, cc, s);
+  };
+  conv(M.enc[0], W.x0.f(), btc(T_max, 512), W.ca.f(), x512, 1);
+  conv(M.enc[1], W.ca.f(), x512, W.cb.f(), x512, 1);
+  conv(M.enc[2], W.cb.f(), x512, W.ca.f(), x512, 1);
+  // (B, T_max, 2048): time-major, so one step's gates of a tile are contiguous
+  conv(M.lstm_in, W.ca.f(), x512, W.gin.f(), btc(T_max, 2048), 0);
   // one cooperative launch for the whole recurrence (W.lc then holds its grid-barrier words; its
   // fill zeroes enc_out too); per-step launches when cooperative launch is unavailable or
   // TTS_ENCODER=steps
@@ -153,36 +138,18 @@ void run_postnet(tts_ctx* c, const float* dec, long dec_b, const int* mlens, int
                  float* out, long out_b, hipStream_t s) {
   auto& M = c->taco;
   auto& W = c->tws;
-  ConvCall cc;
-  cc.lens = mlens;
-  cc.B = B;
-  cc.oflow = x3_flag(c);
-  cc.max_q = max_q;
-  cc.pad_mode = 0;
-  cc.epi = 2;
-  cc.s[0] = src_of(dec, dec_b, 1, 80, 80, 0);
-  cc.out = W.pa.f();
-  cc.ob = (long)512 * Mmax_alloc;
-  cc.oc = Mmax_alloc;
-  cc.ot = 1;
-  run_conv(M.post[0], cc, s);
+  const Layout x512 = bct(512, Mmax_alloc), frames{dec_b, 1, 80};
+  auto conv = [&](const ConvLayer& L, const float* in, Layout li, int Cin, float* o, Layout lo, int epi,
+                  const float* resid) {
+    ConvCall cc = conv_call(c, mlens, B, max_q).in(in, li, Cin).to(o, lo);
+    if (resid) cc.add(resid, frames);
+    cc.epi = epi;
+    run_conv(L, cc, s);
+  };
+  conv(M.post[0], dec, frames, 80, W.pa.f(), x512, 2, nullptr);
   float* bufs[2] = {W.pa.f(), W.pbb.f()};
-  for (int i = 1; i < 4; ++i) {
-    cc.s[0] = src_of(bufs[(i - 1) & 1], (long)512 * Mmax_alloc, Mmax_alloc, 1, 512, 0);
-    cc.out = bufs[i & 1];
-    run_conv(M.post[i], cc, s);
-  }
-  cc.s[0] = src_of(bufs[1], (long)512 * Mmax_alloc, Mmax_alloc, 1, 512, 0);
-  cc.out = out;
-  cc.ob = out_b;
-  cc.oc = 1;
-  cc.ot = 80;
-  cc.epi = 0;
-  cc.resid = dec;
-  cc.rb = dec_b;
-  cc.rc = 1;
-  cc.rt = 80;
-  run_conv(M.post[4], cc, s);
+  for (int i = 1; i < 4; ++i) conv(M.post[i], bufs[(i - 1) & 1], x512, 512, bufs[i & 1], x512, 2, nullptr);
+  conv(M.post[4], bufs[1], x512, 512, out, Layout{out_b, 1, 80}, 0, dec);
 }
 
 template <class T>
@@ -283,16 +250,13 @@ __global__ void taco_mlens_kernel(const DecCtlBlock* cb, int B, int r, int* mlen
 
 // the output mask of a teacher-forced decode: frames [M_i, steps_i r) of decode row i zeroed (at most
 // r - 1 frames: the padded part of the row's last group); one workgroup per row
-struct MelLens {
-  int M[BMAX];
-};
-__global__ void mask_frames_kernel(float* x, MelLens ml, const int* __restrict__ flens, int r, long row) {
+__global__ void mask_frames_kernel(float* x, RowInts ml, const int* __restrict__ flens, int r, long row) {
   const int i = blockIdx.x;
-  const int f0 = ml.M[i], f1 = min(flens[i], f0 + r);  // flens = steps * r <= S_cap r: inside the row
+  const int f0 = ml.v[i], f1 = min(flens[i], f0 + r);  // flens = steps * r <= S_cap r: inside the row
   float* p = x + i * row;
   for (int e = f0 * 80 + threadIdx.x; e < f1 * 80; e += blockDim.x) p[e] = 0.f;
 }
-void mask_frames(float* x, const MelLens& ml, const int* d_flens, int B, int r, long row, hipStream_t s) {
+void mask_frames(float* x, const RowInts& ml, const int* d_flens, int B, int r, long row, hipStream_t s) {
   mask_frames_kernel<<<B, 256, 0, s>>>(x, ml, d_flens, r, row);
   HIP_OK(hipGetLastError());
 }
@@ -617,17 +581,8 @@ void stage_speakers(tts_ctx* c, const int64_t* d_spk_ids, const float* d_spk_emb
 void run_encoder_penc(tts_ctx* c, const int64_t* ids, int B, int T_max, hipStream_t s) {
   auto& W = c->tws;
   run_encoder(c, ids, B, T_max, W.enc.f(), s, W.map.i());
-  ConvCall cc;
-  cc.lens = W.lens.i();
-  cc.B = B;
-  cc.oflow = x3_flag(c);
-  cc.max_q = T_max;
-  cc.s[0] = src_of(W.enc.f(), (long)T_max * 512, 1, 512, 512, 0);
-  cc.out = W.penc.f();
-  cc.ob = (long)T_max * 128;
-  cc.oc = 1;
-  cc.ot = 128;
-  run_conv(c->taco.penc, cc, s);
+  run_conv(c->taco.penc,
+           conv_call(c, W.lens.i(), B, T_max).in(W.enc.f(), btc(T_max, 512), 512).to(W.penc.f(), btc(T_max, 128)), s);
 }
 
 // decoder state and outputs zeroed in one launch (the postnet output too, and the persistent
@@ -662,7 +617,7 @@ void fill_decoder_state(tts_ctx* c, int B, int T_max, int S_cap, int r, bool per
 // frames >= M_i before the postnet, its output after it (the reference's output mask,
 // models/tacotron2.py:123-130)
 void run_postnet_scatter(tts_ctx* c, int B, int T_max, int S_cap, int r, float* d_dec, float* d_post, float* d_align,
-                         float* d_stop, hipStream_t s, const MelLens* ml = nullptr) {
+                         float* d_stop, hipStream_t s, const RowInts* ml = nullptr) {
   auto& W = c->tws;
   taco_mlens_kernel<<<1, 64, 0, s>>>(ctl_block(W), B, r, W.mlens.i());
   HIP_OK(hipGetLastError());
@@ -770,7 +725,7 @@ void ttsh::taco_run(tts_ctx* c, const TacoCall& k) {
     W.pslot_cal = true;
   }
   fill_decoder_state(c, B, T_max, S_cap, r, persist, s);
-  MelLens ml{};  // teacher-forced: the output mask's lengths, decode order
+  RowInts ml{};  // teacher-forced: the output mask's lengths, decode order
   if (t) {  // prenet layer 1 of every ground-truth frame the decoder will be fed, into W.teach
     TeachArgs ta{};
     ta.mel = t->d_mel;
@@ -785,7 +740,7 @@ void ttsh::taco_run(tts_ctx* c, const TacoCall& k) {
     ta.r = r;
     ta.steps = S_cap;
     launch_teacher_prenet(ta, s);
-    for (int i = 0; i < B; ++i) ml.M[i] = t->h_mel_lens[perm[i]];
+    for (int i = 0; i < B; ++i) ml.v[i] = t->h_mel_lens[perm[i]];
   }
   c->dec_path = persist ? 1 : 0;
   if (persist) run_persistent(c, r, W.thr, s, t ? S_cap : 0);
@@ -870,12 +825,11 @@ int tts_taco_encoder(tts_ctx* c, const int64_t* d_ids, const int32_t* h_lens, in
     TTS_CHECK(c && d_ids && h_lens && d_out, "null argument");
     TTS_CHECK(c->taco.ready, "tacotron2 weights not finalized");
     TTS_CHECK(B >= 1 && B <= BMAX && T_max >= 1, "bad sizes");
-    for (int b = 0; b < B; ++b) TTS_CHECK(h_lens[b] >= 1 && h_lens[b] <= T_max, "lens out of range");
+    check_rows(h_lens, B, 1, T_max, "lens out of range");
     DeviceGuard g(c->device);
     taco_workspace(c, B, T_max, std::max(1, c->tws.S_cap), std::max(1, c->tws.r));
     enter(c, stream);
-    std::vector<int> lens(h_lens, h_lens + B);
-    HIP_OK(hipMemcpyAsync(c->tws.lens.p, lens.data(), B * 4, hipMemcpyHostToDevice, c->s));
+    put_rows(c->tws.lens, h_lens, B, c->s);
     with_x3_fallback(c, [&] { run_encoder(c, d_ids, B, T_max, d_out, c->s); });
     check_encoder_barrier(c);
     leave(c, stream);
@@ -895,14 +849,10 @@ int tts_taco_postnet(tts_ctx* c, const float* d_dec, const int32_t* h_lens, int 
     grow<float>(W.pa, (size_t)B * 512 * M_max, gen);
     grow<float>(W.pbb, (size_t)B * 512 * M_max, gen);
     W.gen = gen;
-    int maxM = 0;
-    for (int b = 0; b < B; ++b) {
-      TTS_CHECK(h_lens[b] >= 1 && h_lens[b] <= M_max, "lens out of range");
-      maxM = std::max(maxM, (int)h_lens[b]);
-    }
+    check_rows(h_lens, B, 1, M_max, "lens out of range");
+    const int maxM = *std::max_element(h_lens, h_lens + B);
     enter(c, stream);
-    std::vector<int> lens(h_lens, h_lens + B);
-    HIP_OK(hipMemcpyAsync(W.mlens.p, lens.data(), B * 4, hipMemcpyHostToDevice, c->s));
+    put_rows(W.mlens, h_lens, B, c->s);
     HIP_OK(hipMemsetAsync(d_out, 0, (size_t)B * M_max * 80 * 4, c->s));
     with_x3_fallback(c, [&] {
       run_postnet(c, d_dec, (long)M_max * 80, W.mlens.i(), B, M_max, maxM, d_out, (long)M_max * 80, c->s);

@@ -187,17 +187,11 @@ void run_cbhg(tts_ctx* c, const T1Cbhg& C, const float* x, long xb, int ldx, con
   launch_t1_bigru(W.gin.f(), (long)T * 768, C.gru_whh.f(), C.gru_bhh.f(), lens, B, T, out, ob, s);
 }
 
-void check_rows(const tts_ctx* c, const int32_t* h_lens, int B, int T_max, const char* what) {
+void check_batch(const tts_ctx* c, const int32_t* h_lens, int B, int T_max, const char* what) {
   TTS_CHECK(c->t1.ready, "tacotron1: model not finalized");
   TTS_CHECK(B >= 1 && B <= BMAX, "tacotron1: B must be in [1, " + std::to_string(BMAX) + "]");
   TTS_CHECK(T_max >= 1, std::string("tacotron1: empty ") + what);
-  for (int b = 0; b < B; ++b)
-    TTS_CHECK(h_lens[b] >= 1 && h_lens[b] <= T_max, std::string("tacotron1: ") + what + " length out of range");
-}
-
-void upload_ints(DevBuf& d, const int32_t* h, int n, hipStream_t s) {
-  d.ensure((size_t)n * 4);
-  HIP_OK(hipMemcpyAsync(d.p, h, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  check_rows(h_lens, B, 1, T_max, std::string("tacotron1: ") + what + " length out of range");
 }
 
 // embedding -> Prenet(256 -> 256 -> 128, bias, ReLU) -> CBHG into out (B, T, 256); W.lens holds the lengths
@@ -235,8 +229,8 @@ void t1_infer(tts_ctx* c, const int64_t* d_ids, const int32_t* h_lens, int B, in
   const T1Model& M = c->t1;
   T1WS& W = c->t1ws;
   hipStream_t s = c->s;
-  upload_ints(W.lens, h_lens, B, s);
-  upload_ints(W.msteps, h_max_steps, B, s);
+  put_rows(W.lens, h_lens, B, s);
+  put_rows(W.msteps, h_max_steps, B, s);
   W.ctl.ensure((size_t)3 * B * 4);
   W.enc.ensure((size_t)B * T * 256 * 4);
   W.pin.ensure((size_t)B * T * 128 * 4);
@@ -312,12 +306,12 @@ int tts_tacotron1_encoder(tts_ctx* c, const int64_t* d_ids, const int32_t* h_len
       c, stream,
       [&] {
         TTS_CHECK(d_ids && h_lens && d_out, "null argument");
-        check_rows(c, h_lens, B, T_max, "text");
+        check_batch(c, h_lens, B, T_max, "text");
       },
       [&] {
-        upload_ints(c->t1ws.lens, h_lens, B, c->s);
+        put_rows(c->t1ws.lens, h_lens, B, c->s);
         run_encoder(c, d_ids, B, T_max, d_out);
-        HIP_OK(hipStreamSynchronize(c->s));  // h_lens is the caller's
+        HIP_OK(hipStreamSynchronize(c->s));
       });
 }
 
@@ -327,10 +321,10 @@ int tts_tacotron1_postnet(tts_ctx* c, const float* d_dec, const int32_t* h_lens,
       c, stream,
       [&] {
         TTS_CHECK(d_dec && h_lens && d_out, "null argument");
-        check_rows(c, h_lens, B, M_max, "mel");
+        check_batch(c, h_lens, B, M_max, "mel");
       },
       [&] {
-        upload_ints(c->t1ws.lens, h_lens, B, c->s);
+        put_rows(c->t1ws.lens, h_lens, B, c->s);
         run_postnet(c, d_dec, (long)M_max * 80, c->t1ws.lens.i(), B, M_max, d_out, (long)M_max * c->t1.post_dim);
         HIP_OK(hipStreamSynchronize(c->s));
       });
@@ -344,11 +338,11 @@ int tts_tacotron1_infer(tts_ctx* c, const int64_t* d_ids, const int32_t* h_lens,
       [&] {
         TTS_CHECK(d_ids && h_lens && h_max_steps && d_dec && d_post && d_align && d_stop && h_steps && h_status,
                   "null argument");
-        check_rows(c, h_lens, B, T_max, "text");
+        check_batch(c, h_lens, B, T_max, "text");
         TTS_CHECK(T_max <= T1_T_MAX, "tacotron1: more than " + std::to_string(T1_T_MAX) + " input positions");
         TTS_CHECK(r >= 1 && r <= c->t1.r_init, "tacotron1: r must be in [1, r_init]");
-        for (int b = 0; b < B; ++b)  // a row that never stops runs max_decoder_steps + 1 steps
-          TTS_CHECK(h_max_steps[b] >= 1 && h_max_steps[b] + 1 <= S_cap, "tacotron1: S_cap must be > max_decoder_steps >= 1");
+        // a row that never stops runs max_decoder_steps + 1 steps
+        check_rows(h_max_steps, B, 1, (long)S_cap - 1, "tacotron1: S_cap must be > max_decoder_steps >= 1");
       },
       [&] {
         t1_infer(c, d_ids, h_lens, B, T_max, r, h_max_steps, S_cap, d_dec, d_post, d_align, d_stop, h_steps,

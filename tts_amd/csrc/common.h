@@ -13,6 +13,12 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BMAX = 64;  // utterances per call (Bp <= 64)
 
+// Per-call row values (lengths, ids) passed by value as a kernel argument: the launch copies them,
+// so a call needs no host-to-device copy and no host buffer that has to outlive it
+struct RowInts {
+  int v[BMAX];
+};
+
 // 16x16x4 f32-in / f32-accumulate MFMA (exact f32, k-ordered fma chain).
 // Operand lane maps (cdna_hip_programming.md §3): A[i=l&15][k=l>>4], B[k=l>>4][j=l&15];
 // D: col j = l&15, row i = 4*(l>>4) + reg.

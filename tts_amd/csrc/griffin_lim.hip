@@ -34,7 +34,7 @@ template <bool START>
 __global__ void __launch_bounds__(LANES) gl_frame_kernel(const float* __restrict__ S, const float* __restrict__ u,
                                                          const float* __restrict__ Fin, float* __restrict__ Fout,
                                                          const float* __restrict__ env, const float2* __restrict__ W,
-                                                         const float* __restrict__ win, GlLens lens, int M_max,
+                                                         const float* __restrict__ win, RowInts lens, int M_max,
                                                          int hop, int wlo, int whi, long env_stride) {
   __shared__ float2 buf[BUF];
   const int t = blockIdx.x, b = blockIdx.y, j = threadIdx.x, M = lens.v[b];
@@ -52,7 +52,7 @@ __global__ void __launch_bounds__(LANES) gl_frame_kernel(const float* __restrict
 }
 
 // window-square envelope of each row's overlap-add, over the padded signal: grid (ceil(P/256), B)
-__global__ void gl_env_kernel(float* __restrict__ env, const float* __restrict__ win, GlLens lens, int hop, int wlo,
+__global__ void gl_env_kernel(float* __restrict__ env, const float* __restrict__ win, RowInts lens, int hop, int wlo,
                               int whi, long env_stride) {
   const int b = blockIdx.y, M = lens.v[b];
   const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -71,7 +71,7 @@ __global__ void gl_env_kernel(float* __restrict__ env, const float* __restrict__
 
 // the last overlap-add: wav (B, Lmax), row b zero past hop (lens[b] - 1)
 __global__ void gl_finish_kernel(const float* __restrict__ F, const float* __restrict__ env, float* __restrict__ wav,
-                                 GlLens lens, int M_max, int hop, int wlo, int whi, long env_stride, int Lmax) {
+                                 RowInts lens, int M_max, int hop, int wlo, int whi, long env_stride, int Lmax) {
   const int b = blockIdx.y, M = lens.v[b];
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= Lmax) return;
@@ -84,7 +84,7 @@ __global__ void gl_finish_kernel(const float* __restrict__ F, const float* __res
 // block: the frames' amplitudes in LDS, each thread one bin of all the frames (plain FMA: 513 x 80)
 constexpr int MEL_TF = 8, MEL_THREADS = 256;
 __global__ void __launch_bounds__(MEL_THREADS)
-    mel_to_linear_kernel(const float* __restrict__ mel, GlLens lens, int M_max, int n_mels, int F,
+    mel_to_linear_kernel(const float* __restrict__ mel, RowInts lens, int M_max, int n_mels, int F,
                          const float* __restrict__ inv, const float* __restrict__ scale,
                          const float* __restrict__ offset, float clip_lo, float clip_hi, int use_clip, float gain,
                          float power, float* __restrict__ S) {
@@ -117,7 +117,7 @@ __global__ void __launch_bounds__(MEL_THREADS)
 
 }  // namespace
 
-void launch_gl_env(float* env, const float* win, const GlLens& lens, int B, int M_max, int hop, int wlo, int whi,
+void launch_gl_env(float* env, const float* win, const RowInts& lens, int B, int M_max, int hop, int wlo, int whi,
                    long env_stride, hipStream_t s) {
   const long P = (long)hop * (M_max - 1) + gl::NFFT;
   gl_env_kernel<<<dim3((unsigned)((P + 255) / 256), B), 256, 0, s>>>(env, win, lens, hop, wlo, whi, env_stride);
@@ -125,7 +125,7 @@ void launch_gl_env(float* env, const float* win, const GlLens& lens, int B, int 
 }
 
 void launch_gl_frames(bool start, const float* S, const float* u, const float* Fin, float* Fout, const float* env,
-                      const float* W, const float* win, const GlLens& lens, int B, int M_max, int hop, int wlo,
+                      const float* W, const float* win, const RowInts& lens, int B, int M_max, int hop, int wlo,
                       int whi, long env_stride, hipStream_t s) {
   const dim3 grid(M_max, B);
   const float2* W2 = reinterpret_cast<const float2*>(W);
@@ -138,7 +138,7 @@ void launch_gl_frames(bool start, const float* S, const float* u, const float* F
   HIP_OK(hipGetLastError());
 }
 
-void launch_gl_finish(const float* F, const float* env, float* wav, const GlLens& lens, int B, int M_max, int hop,
+void launch_gl_finish(const float* F, const float* env, float* wav, const RowInts& lens, int B, int M_max, int hop,
                       int wlo, int whi, long env_stride, hipStream_t s) {
   const int Lmax = hop * (M_max - 1);
   if (Lmax <= 0) return;
@@ -147,7 +147,7 @@ void launch_gl_finish(const float* F, const float* env, float* wav, const GlLens
   HIP_OK(hipGetLastError());
 }
 
-void launch_mel_to_linear(const float* mel, const GlLens& lens, int B, int M_max, int n_mels, int F, const float* inv,
+void launch_mel_to_linear(const float* mel, const RowInts& lens, int B, int M_max, int n_mels, int F, const float* inv,
                           const float* scale, const float* offset, float clip_lo, float clip_hi, int use_clip,
                           float spec_gain, float power, float* S, hipStream_t s) {
   mel_to_linear_kernel<<<dim3((M_max + MEL_TF - 1) / MEL_TF, B), MEL_THREADS, MEL_TF * n_mels * sizeof(float), s>>>(

@@ -34,7 +34,7 @@ __device__ __forceinline__ float sum4(const float* a) { return (a[0] + a[1]) + (
 // of a group). Per output element the sum runs over (kt, kh, ci) ascending, ci in 4 chains.
 template <int CIN, int COUT>
 __global__ __launch_bounds__(256) void gst_conv_kernel(const float* __restrict__ in, long in_b, int Wi_max, int Hi,
-                                                       GstLens lens, int layer, const float* __restrict__ W,
+                                                       RowInts lens, int layer, const float* __restrict__ W,
                                                        const float* __restrict__ bias, float* __restrict__ out,
                                                        long out_b, int Ho) {
   constexpr int P = 4, NG = 256 / COUT, Q = CIN == 1 ? 1 : 4;
@@ -98,7 +98,7 @@ __global__ __launch_bounds__(256) void gst_conv_kernel(const float* __restrict__
 }
 
 template <int CIN, int COUT>
-void conv_layer(const float* in, long in_b, int Wi_max, int Hi, const GstLens& lens, int layer, const float* W,
+void conv_layer(const float* in, long in_b, int Wi_max, int Hi, const RowInts& lens, int layer, const float* W,
                 const float* bias, float* out, int B, hipStream_t s) {
   const int Wo_max = (Wi_max + 1) / 2, Ho = (Hi + 1) / 2;
   const int per_block = (256 / COUT) * 4;
@@ -226,7 +226,7 @@ __global__ void gst_tokens_kernel(GstTokenArgs a, const float* __restrict__ Vt, 
 
 }  // namespace
 
-void launch_gst_convs(const float* mel, const GstLens& lens, int B, int N_max, const float* const* W,
+void launch_gst_convs(const float* mel, const RowInts& lens, int B, int N_max, const float* const* W,
                       const float* const* bias, float* bufA, float* bufB, hipStream_t s) {
   TTS_CHECK(B >= 1 && B <= 64 && N_max >= 1, "gst convs: sizes");
   int w = N_max;

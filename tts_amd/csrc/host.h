@@ -54,6 +54,25 @@ struct DevBuf {
   int* i() const { return static_cast<int*>(p); }
   const uint16_t* h() const { return static_cast<const uint16_t*>(p); }
 };
+template <class T>
+void ensure(DevBuf& b, size_t n) {  // room for n elements of T
+  b.ensure(n * sizeof(T));
+}
+
+// Per-call row values (lengths, ids) to the device, on stream s: a one-block kernel takes them by
+// value (RowInts), BMAX per launch, so nothing reads the host array after the call returns and no
+// copy from pageable memory stalls the stream. put_rows returns dst; fill_rows writes n copies of
+// one value. The DevBuf forms grow dst to n ints first.
+inline RowInts row_ints(const int32_t* h, int n) {  // n <= BMAX values, the rest zero
+  RowInts r{};
+  std::copy(h, h + n, r.v);
+  return r;
+}
+const int* put_rows(int* dst, const int32_t* h, int n, hipStream_t s);
+const int* put_rows(DevBuf& dst, const int32_t* h, int n, hipStream_t s);
+const int* fill_rows(DevBuf& dst, int value, int n, hipStream_t s);
+// every h[b], b < n, inside [lo, hi], or msg is thrown
+void check_rows(const int32_t* h, int n, long lo, long hi, const std::string& msg);
 
 // split-f16 A fragments (split16.h pack_split_a) of a row-major (rows x K) matrix, rows and K
 // multiples of 16 and 32; the buffer stays empty when a weight is outside the f16 range (the
@@ -94,7 +113,21 @@ void pack_conv(ConvLayer& L, const std::vector<float>& Wm, const std::vector<flo
 void pack_conv_x3_only(ConvLayer& L, const std::vector<float>& Wm, const std::vector<float>& bias, int Cin, int Cout,
                        int K);
 
+// The two activation layouts as {batch, channel, time} strides in elements
+struct Layout {
+  long b;
+  int c, t;
+};
+inline Layout bct(int C, long T) { return {(long)C * T, (int)T, 1}; }  // (B, C, T)
+inline Layout btc(long T, int C) { return {T * C, 1, C}; }              // (B, T, C)
+
+// One conv launch. conv_call() (below) starts a record; in / in2 / to / add set the sources, the
+// output and the residual by pointer + layout; everything else is set by name at the site.
 struct ConvCall {
+  ConvCall& in(const float* p, Layout l, int C, int act = 0) { return s[0] = ConvSrc{p, l.b, l.c, l.t, C, act}, *this; }
+  ConvCall& in2(const float* p, Layout l, int C) { return s[1] = ConvSrc{p, l.b, l.c, l.t, C, 0}, nsrc = 2, *this; }
+  ConvCall& to(float* p, Layout l) { return out = p, ob = l.b, oc = l.c, ot = l.t, *this; }
+  ConvCall& add(const float* p, Layout l) { return resid = p, rb = l.b, rc = l.c, rt = l.t, *this; }
   ConvSrc s[2];
   int nsrc = 1;
   int pad_mode = 0;
@@ -115,8 +148,6 @@ struct ConvCall {
 };
 
 void run_conv(const ConvLayer& L, const ConvCall& c, hipStream_t st);
-
-inline ConvSrc src_of(const float* p, long sb, int sc, int st, int C, int act) { return ConvSrc{p, sb, sc, st, C, act}; }
 
 // weight layout helpers: LSTM gate rows regrouped per 4-unit tile, column blocks of matrices with
 // equal row counts concatenated, a column range, swizzle_rows16 with the rows padded to 16, and a
@@ -327,12 +358,11 @@ struct GlowWS {
   DevBuf ids, lens, klens, ylens, xa, xb, h2, hdp, logw, cum, wceil, om, z, sq, sq2, whs, wacts, big;
   DevBuf spk, ones, g, gcond;  // speaker ids, unit lengths, normalized g (B, c_pad), cond biases
   bool has_g = false;          // the last glow_encode was given speaker ids
-  std::vector<int> h_ylens, h_klens, h_spk;
+  std::vector<int> h_xlens, h_ylens;  // the last glow_encode's lengths, for glow_decode / glow_align
   // GlowTts.forward (glow_align) and the stand-alone alignment search (glow_mas): even mel lengths,
   // their halves, the end conv's plain output, log-determinant partials, the likelihood matrix, the
   // search's decision words and the frame -> token map
   DevBuf aylens, aklens, eo, ldpart, logp, masbits, xof, mxl, myl;
-  std::vector<int> h_xlens, h_aylens, h_aklens, h_mxl, h_myl;
 };
 
 // ParallelWaveGAN generator (TTS/vocoder/models/parallel_wavegan_generator.py, setup_generator's
@@ -472,6 +502,17 @@ inline unsigned* x3_flag(tts_ctx* c) {
   return reinterpret_cast<unsigned*>(c->x3flag.p);
 }
 
+// a conv over B rows of lens (device) positions, max_q of them at most, on the context's kernels:
+// split-f16 with the call's range flag, or fp32
+inline ConvCall conv_call(tts_ctx* c, const int* lens, int B, int max_q) {
+  ConvCall cc;
+  cc.lens = lens;
+  cc.B = B;
+  cc.max_q = max_q;
+  cc.oflow = x3_flag(c);
+  return cc;
+}
+
 struct DeviceGuard {
   int prev = -1;
   explicit DeviceGuard(int d) {
@@ -489,6 +530,7 @@ struct DeviceGuard {
 void enter(tts_ctx* c, void* stream, bool join_voc = true);
 void leave(tts_ctx* c, void* stream);
 
+// the Tacotron2 workspace's form of ensure<T>: counts the reallocations its cached graphs depend on
 template <class T>
 bool grow(DevBuf& b, size_t n, long& gen) {
   if (b.ensure(n * sizeof(T))) {

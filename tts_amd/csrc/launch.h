@@ -2,6 +2,7 @@
 // glow.hip, glow_forward.hip, pwgan.hip). Each is declared here only; the file that defines it includes this header,
 // so the compiler checks the signature against the definition.
 #pragma once
+#include "common.h"  // RowInts
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <vector>
@@ -111,16 +112,13 @@ struct T1DecArgs {
 };
 void launch_t1_decoder(const T1DecArgs& a, int B, hipStream_t s);
 
-// gst.hip (Global Style Tokens). Row lengths (mel frames) travel as a kernel argument.
+// gst.hip (Global Style Tokens). Row lengths (mel frames) travel as a kernel argument (RowInts).
 constexpr int GST_HG_MAX = 256, GST_G_MAX = 512, GST_ES_MAX = 1024, GST_HEADS_MAX = 8, GST_TOK_MAX = 32,
               GST_DICT_MAX = 64;
-struct GstLens {
-  int v[64];
-};
 // the six reference-encoder layers: mel (B, N_max, 80) -> bufB (B, W6, 2, 128), W_l = ceil(W_{l-1} / 2)
 // of N_max; W[l] is [3][3][Cin][Cout] with BatchNorm folded, bias[l] the folded bias. bufA holds
 // layer 1's output (B, W1, 40, 32), bufB layer 2's (B, W2, 20, 32); later layers alternate.
-void launch_gst_convs(const float* mel, const GstLens& lens, int B, int N_max, const float* const* W,
+void launch_gst_convs(const float* mel, const RowInts& lens, int B, int N_max, const float* const* W,
                       const float* const* bias, float* bufA, float* bufB, hipStream_t s);
 // GRU over x (B, W6, 256) ([mel bin][channel] features), then the style-token attention -> out (B, G).
 // wihT [256][3 Hg], whhT [Hg][3 Hg] (gates r | z | n), wqT [Hg + Es][G], Kt / Vt [ntok][G];
@@ -128,7 +126,7 @@ void launch_gst_convs(const float* mel, const GstLens& lens, int B, int N_max, c
 struct GstHeadArgs {
   const float* x;
   long xb;
-  GstLens lens;
+  RowInts lens;
   const float *wihT, *whhT, *bih, *bhh, *wqT, *Kt, *Vt, *spk;
   int Hg, G, heads, ntok, Es;
   float scale;
@@ -143,31 +141,28 @@ struct GstTokenArgs {
 };
 void launch_gst_tokens(const GstTokenArgs& a, const float* Vt, int G, int ntok, float* out, hipStream_t s);
 
-// griffin_lim.hip. Row lengths travel as a kernel argument (at most 64 rows), so a call needs no
-// host-to-device copy. W = e^{-2 pi i m / 1024} (1024 complex), win = the window zero-padded to
+// griffin_lim.hip. Row lengths travel as a kernel argument (RowInts: at most 64 rows), so a call
+// needs no host-to-device copy. W = e^{-2 pi i m / 1024} (1024 complex), win = the window zero-padded to
 // 1024, nonzero inside [wlo, whi); env (B, env_stride) the rows' window-square envelopes; F
 // (B, M_max, 1024) windowed frames.
-struct GlLens {
-  int v[64];
-};
-void launch_gl_env(float* env, const float* win, const GlLens& lens, int B, int M_max, int hop, int wlo, int whi,
+void launch_gl_env(float* env, const float* win, const RowInts& lens, int B, int M_max, int hop, int wlo, int whi,
                    long env_stride, hipStream_t s);
 void launch_gl_frames(bool start, const float* S, const float* u, const float* Fin, float* Fout, const float* env,
-                      const float* W, const float* win, const GlLens& lens, int B, int M_max, int hop, int wlo,
+                      const float* W, const float* win, const RowInts& lens, int B, int M_max, int hop, int wlo,
                       int whi, long env_stride, hipStream_t s);
-void launch_gl_finish(const float* F, const float* env, float* wav, const GlLens& lens, int B, int M_max, int hop,
+void launch_gl_finish(const float* F, const float* env, float* wav, const RowInts& lens, int B, int M_max, int hop,
                       int wlo, int whi, long env_stride, hipStream_t s);
-void launch_mel_to_linear(const float* mel, const GlLens& lens, int B, int M_max, int n_mels, int F, const float* inv,
+void launch_mel_to_linear(const float* mel, const RowInts& lens, int B, int M_max, int n_mels, int F, const float* inv,
                           const float* scale, const float* offset, float clip_lo, float clip_hi, int use_clip,
                           float spec_gain, float power, float* S, hipStream_t s);
 
 // stft.hip. nsamp holds the rows' sample counts (by value, as above); W = e^{-2 pi i m / n_fft}
 // (n_fft complex), win = the window zero-padded to n_fft, nonzero inside [wlo, whi). fft: the
 // 1024-point FFT kernel (n_fft must be 1024), else the direct DFT. out (B, M_max, n_fft / 2 + 1).
-void launch_stft_frames(bool fft, const float* wav, long L_max, const GlLens& nsamp, int B, int M_max, int n_fft,
+void launch_stft_frames(bool fft, const float* wav, long L_max, const RowInts& nsamp, int B, int M_max, int n_fft,
                         int hop, int wlo, int whi, float preemph, const float* W, const float* win, float* out,
                         hipStream_t s);
 // mag (B, M_max, F) -> out (B, M_max, C); basis (C, F) or null (then C == F)
-void launch_mag_to_feature(const float* mag, const GlLens& lens, int B, int M_max, int F, int C, const float* basis,
+void launch_mag_to_feature(const float* mag, const RowInts& lens, int B, int M_max, int F, int C, const float* basis,
                            float gain, const float* scale, const float* offset, float clip_lo, float clip_hi,
                            int use_clip, float* out, hipStream_t s);

@@ -29,7 +29,7 @@ __device__ __forceinline__ void fft512(float2* buf, const float2* __restrict__ W
 
 // grid (M_max, B), 64 threads: |STFT| of frame t of row b, 513 bins. nsamp.v[b] = samples of row b;
 // frames t >= 1 + nsamp / hop read nothing and are written as zeros.
-__global__ void __launch_bounds__(LANES) stft_frame_kernel(const float* __restrict__ wav, long L_max, GlLens nsamp,
+__global__ void __launch_bounds__(LANES) stft_frame_kernel(const float* __restrict__ wav, long L_max, RowInts nsamp,
                                                            const float2* __restrict__ W,
                                                            const float* __restrict__ win, int M_max, int hop, int wlo,
                                                            int whi, float preemph, float* __restrict__ out) {
@@ -50,7 +50,7 @@ __global__ void __launch_bounds__(LANES) stft_frame_kernel(const float* __restri
 // Thread-strided bins, each a direct sum over the window's support.
 constexpr int DFT_THREADS = 256;
 __global__ void __launch_bounds__(DFT_THREADS) dft_frame_kernel(const float* __restrict__ wav, long L_max,
-                                                                GlLens nsamp, const float2* __restrict__ W,
+                                                                RowInts nsamp, const float2* __restrict__ W,
                                                                 const float* __restrict__ win, int M_max, int n_fft,
                                                                 int hop, int wlo, int whi, float preemph,
                                                                 float* __restrict__ out) {
@@ -77,7 +77,7 @@ __global__ void __launch_bounds__(DFT_THREADS) dft_frame_kernel(const float* __r
 // of all the frames (plain FMA), the mirror of mel_to_linear_kernel
 constexpr int FEAT_TF = 8, FEAT_THREADS = 256;
 __global__ void __launch_bounds__(FEAT_THREADS)
-    mag_to_feature_kernel(const float* __restrict__ mag, GlLens lens, int M_max, int F, int C,
+    mag_to_feature_kernel(const float* __restrict__ mag, RowInts lens, int M_max, int F, int C,
                           const float* __restrict__ basis, float gain, const float* __restrict__ scale,
                           const float* __restrict__ offset, float clip_lo, float clip_hi, int use_clip,
                           float* __restrict__ out) {
@@ -113,7 +113,7 @@ __global__ void __launch_bounds__(FEAT_THREADS)
 
 }  // namespace
 
-void launch_stft_frames(bool fft, const float* wav, long L_max, const GlLens& nsamp, int B, int M_max, int n_fft,
+void launch_stft_frames(bool fft, const float* wav, long L_max, const RowInts& nsamp, int B, int M_max, int n_fft,
                         int hop, int wlo, int whi, float preemph, const float* W, const float* win, float* out,
                         hipStream_t s) {
   const dim3 grid(M_max, B);
@@ -128,7 +128,7 @@ void launch_stft_frames(bool fft, const float* wav, long L_max, const GlLens& ns
   HIP_OK(hipGetLastError());
 }
 
-void launch_mag_to_feature(const float* mag, const GlLens& lens, int B, int M_max, int F, int C, const float* basis,
+void launch_mag_to_feature(const float* mag, const RowInts& lens, int B, int M_max, int F, int C, const float* basis,
                            float gain, const float* scale, const float* offset, float clip_lo, float clip_hi,
                            int use_clip, float* out, hipStream_t s) {
   mag_to_feature_kernel<<<dim3((M_max + FEAT_TF - 1) / FEAT_TF, B), FEAT_THREADS, FEAT_TF * F * sizeof(float), s>>>(
