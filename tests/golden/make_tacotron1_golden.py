@@ -7,6 +7,9 @@ Run by hand on a machine that has the reference checkout (``TTS_REFERENCE``, def
 * ``tacotron1_*.npz``: seed, config JSON, weight gains and, per reduction factor r and utterance i,
   ``r{r}_u{i}_{ids,dec,post,align,stop,logit,top2,drift64}`` (+ ``_enc`` for utterance 1), with the
   per-r ``r{r}_seed``, ``r{r}_stop_bias`` and ``r{r}_max_steps``, in the shape of ``taco_*.npz``.
+* ``tacotron1_f64.npz`` (``python make_tacotron1_golden.py f64``, which leaves the files above as they
+  are): the reference run in float64 on the same utterances and on the new cases ``F64_CASES``, the
+  pin of ``oracle/tacotron1_np.py``; see ``f64_file``.
 
 Weights come from ``synth_state_dict(tacotron_spec(cfg), seed, gains)``. The stop rule of
 ``Decoder.inference`` (layers/tacotron.py:489-494) is: after step t, stop if t > T/4 and
@@ -15,7 +18,6 @@ never fed back, so one never-stopping run gives the bias-free logits, and the st
 chosen for the widest margin around logit(0.6). The conditions the issue sets are asserted below.
 """
 import json
-import math
 import os
 import sys
 
@@ -25,7 +27,9 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.dirname(HERE))
 
+from helpers import L06, choose_bias, pack_f64  # noqa: E402
 from tts_amd.spec import TacotronV1Config, tacotron_spec  # noqa: E402
 from tts_amd.weights import synth_state_dict  # noqa: E402
 
@@ -38,7 +42,6 @@ from TTS.tts.models.tacotron import Tacotron  # noqa: E402
 torch.set_num_threads(8)
 
 MEL_TOL = 1e-4
-L06 = math.log(0.6 / 0.4)
 STOP_W = "decoder.stopnet.linear.weight"
 STOP_B = "decoder.stopnet.linear.bias"
 # per-kind weight scales: a larger stop weight widens the stop margins; the others keep every
@@ -79,39 +82,6 @@ def run(m, ids, r, max_steps, dtype=torch.float32):
         torch.set_default_dtype(torch.float32)
     return (dec[0].double().numpy(), post[0].double().numpy(), align[0].double().numpy(),
             stop[0, :, 0].double().numpy(), torch.cat(sin, 0).double().numpy(), enc[0].double().numpy())
-
-
-def choose_bias(raw, Ts, aligns, max_steps, min_token_stops, need_max_row, min_stop_step=3):
-    """Stop bias with the widest margin |l_t + b - logit(0.6)| over the tested steps (t > T/4, up to
-    each row's stop), such that at least min_token_stops rows stop by the token (not before
-    min_stop_step) and, if asked, a row runs max_steps + 1 steps."""
-    elig = [np.arange(len(l)) + 1 > T / 4 for l, T in zip(raw, Ts)]
-    cands = np.sort(np.concatenate([L06 - l[e] for l, e in zip(raw, elig)]))
-    best = None
-    for b in (cands[:-1] + cands[1:]) / 2:
-        margins, ntok, nmax, ok = [], 0, 0, True
-        for l, e, a, T in zip(raw, elig, aligns, Ts):
-            z = l + b - L06
-            by_align = e & (a[:len(l), T - 1] > 0.6)
-            idx_tok = np.nonzero(e & (z > 0))[0]
-            idx_al = np.nonzero(by_align)[0]
-            s_tok = idx_tok[0] if len(idx_tok) else len(l)
-            s_al = idx_al[0] if len(idx_al) else len(l)
-            end = min(s_tok, s_al, len(l) - 1)
-            if s_tok < s_al:
-                ntok += 1
-                ok &= s_tok + 1 >= min_stop_step
-            elif s_al == len(l) and len(l) == max_steps + 1:
-                nmax += 1
-            tested = e[:end + 1]
-            if tested.any():
-                margins.append(np.abs(z[:end + 1][tested]).min())
-        if not ok or ntok < min_token_stops or (need_max_row and nmax < 1):
-            continue
-        mm = min(margins)
-        if best is None or mm > best[1]:
-            best = (float(b), float(mm), ntok, nmax)
-    return best
 
 
 def case(name, cfg, seed, utt_lens, r_list, max_steps, min_token_stops, need_max_row, id_seed, gains=None):
@@ -217,6 +187,108 @@ def keys_file():
         json.dump(out, f, indent=0)
 
 
+# ---- tacotron1_f64.npz: the reference in float64 (the pin of oracle/tacotron1_np.py) ----
+EXISTING = ("tacotron1_sigmoid", "tacotron1_softmax_last", "tacotron1_mem3", "tacotron1_linear1025")
+NEVER = -1e4  # stop bias of the new cases: the token never stops a row
+# (tag, memory_size, r_init, attn_norm, r run, T, max_steps, first seed); T > 4 (max_steps + 1), so the
+# stop rule is never evaluated. What each exercises in tacotron1.hip is in tests/test_tacotron1_edges_gpu.py.
+F64_CASES = [
+    ("q32", 32, 5, "sigmoid", [1, 3], 150, 35, 51),
+    ("q14", 14, 5, "sigmoid", [1], 100, 20, 52),
+    ("q32r10", 32, 10, "sigmoid", [10], 40, 8, 53),
+    ("q5r1", 5, 1, "sigmoid", [1], 30, 6, 54),
+    ("last7", -1, 7, "softmax", [7, 2], 60, 6, 55),
+    ("long_sigmoid", 5, 5, "sigmoid", [5], 1024, 5, 56),
+    ("long_softmax", 5, 5, "softmax", [5], 1023, 5, 57),
+]
+LONG_EXTRA = {"long_sigmoid": (257, 9, 1), "long_softmax": (257,)}  # the other rows of the ragged GPU calls (ids only)
+# utterances whose post is stored (129-wide); the others are left out to keep the file under 500 KB
+F64_POST = {"tacotron1_sigmoid.r5_u0", "tacotron1_sigmoid.r5_u1", "tacotron1_sigmoid.r2_u0", "tacotron1_sigmoid.r2_u1",
+            "tacotron1_softmax_last.r5_u0", "q5r1.r1", "last7.r2"}
+_grid = pack_f64
+
+
+def f64_file():
+    """tests/golden/tacotron1_f64.npz: the reference's float64 outputs (dec, align, stop, logit) for
+    every (file, r, utterance) of the four float32 fixtures, keyed ``{file}.r{r}_u{i}_*``, and for the
+    new cases F64_CASES, keyed ``{tag}.r{r}_*`` with ``{tag}.ids``. The two long cases hold encoder
+    rows {0, 1, 511, 512, T-2, T-1} (``_enc``) and no post. Weights are regenerated from the stored
+    seeds and gains.
+
+    Size: raw float64 arrays of all of this take 1 MB, so (a) every array is stored as helpers.pack_f64
+    does, fixed point in multiples of 2^-38 (a rounding error of 1.8e-12, against the 1e-9 the oracle is
+    held to), read back with helpers.unpack_f64; (b) post is stored for the utterances in F64_POST only:
+    of the 129-wide models' utterances it is left out for tacotron1_sigmoid r5 u2 / u3 and r2 u2 / u3,
+    tacotron1_softmax_last u1, tacotron1_mem3 u0 / u1, q32 (r 1 and 3), q14, q32r10 and last7 r 7. The
+    float32 fixtures pin the oracle's post for every one of their utterances to their own drift64."""
+    out = {}
+
+    def store(k, res):
+        dec, po, align, stop, sin, enc = res
+        out[k + "_dec"], out[k + "_align"], out[k + "_stop"] = _grid(dec), _grid(align), _grid(stop)
+        if k in F64_POST:
+            out[k + "_post"] = _grid(po)
+
+    for name in EXISTING:
+        fx = np.load(os.path.join(HERE, name + ".npz"))
+        cfg = TacotronV1Config(**json.loads(str(fx["cfg"])))
+        for r in (int(v) for v in fx["r_list"]):
+            sd = synth_state_dict(tacotron_spec(cfg), int(fx[f"r{r}_seed"]), json.loads(str(fx["overrides"])))
+            sd[STOP_B] = np.array([float(fx[f"r{r}_stop_bias"])], np.float32)
+            m64 = build(cfg, sd, torch.float64)
+            i = 0
+            while f"r{r}_u{i}_ids" in fx.files:
+                res = run(m64, fx[f"r{r}_u{i}_ids"], r, int(fx[f"r{r}_max_steps"]), torch.float64)
+                assert len(res[3]) == len(fx[f"r{r}_u{i}_stop"]), "the float64 run stops elsewhere"
+                k = f"{name}.r{r}_u{i}"
+                store(k, res)
+                out[k + "_logit"] = _grid(res[4] @ sd[STOP_W].astype(np.float64)[0] + np.float64(sd[STOP_B][0]))
+                i += 1
+    cases = []
+    for tag, mem, r_init, norm, r_list, T, ms, seed in F64_CASES:
+        cfg = TacotronV1Config(memory_size=mem, r=r_init, attn_norm=norm, postnet_output_dim=129)
+        assert T > 4 * (ms + 1)
+        rs = np.random.RandomState(1000 + seed)
+        ids = rs.randint(1, cfg.num_chars, size=T).astype(np.int64)
+        extra = {n: rs.randint(1, cfg.num_chars, size=n).astype(np.int64) for n in LONG_EXTRA.get(tag, ())}
+        long = tag in LONG_EXTRA
+        for attempt in range(20):
+            sd = synth_state_dict(tacotron_spec(cfg), seed, GAINS)
+            sd[STOP_B] = np.array([NEVER], np.float32)
+            m32, m64 = build(cfg, sd), build(cfg, sd, torch.float64)
+            runs, drift, ok = {}, 0.0, True
+            for r in r_list:
+                a, b = run(m32, ids, r, ms), run(m64, ids, r, ms, torch.float64)
+                assert len(a[3]) == len(b[3]) == ms + 1
+                drift = max(drift, float(np.abs(a[0] - b[0]).max()), float(np.abs(a[1] - b[1]).max()))
+                runs[r] = b
+            for n, x in extra.items():  # rows that do reach the alignment rule: the fixtures' margin
+                al = run(m64, x, r_list[0], ms, torch.float64)[2]
+                t = np.arange(len(al)) + 1
+                ok &= bool(np.abs(al[t > n / 4, n - 1] - 0.6).min() >= 1e-3) if (t > n / 4).any() else True
+            if 8 * drift <= MEL_TOL and ok:
+                break
+            seed += 1
+        else:
+            raise SystemExit(f"[{tag}] no seed with 8 x drift64 <= MEL_TOL")
+        print(f"[{tag}] seed {seed} drift64 {drift:.2e} (8 x = {8 * drift:.2e})")
+        out[f"{tag}.ids"] = ids
+        for n, x in extra.items():
+            out[f"{tag}.ids{n}"] = x
+        for r in r_list:
+            store(f"{tag}.r{r}", runs[r])
+            out[f"{tag}.r{r}_logit"] = _grid(runs[r][4] @ sd[STOP_W].astype(np.float64)[0] + NEVER)
+            if long:
+                out[f"{tag}.r{r}_enc"] = _grid(runs[r][5][[0, 1, 511, 512, T - 2, T - 1]])
+        cases.append({"tag": tag, "cfg": cfg.__dict__, "seed": seed, "r_list": r_list, "max_steps": ms,
+                      "stop_bias": NEVER, "extra": list(extra)})
+    out["cases"] = json.dumps(cases)
+    out["overrides"] = json.dumps(GAINS)
+    path = os.path.join(HERE, "tacotron1_f64.npz")
+    np.savez_compressed(path, **out)
+    print(f"[tacotron1_f64] {os.path.getsize(path) / 1024:.0f} KiB")
+
+
 def main():
     keys_file()
     tot = {"token": 0, "max": 0, "bank": 0.0, "gru": 0.0}
@@ -247,4 +319,7 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["f64"]:  # the float64 file alone; the four float32 fixtures stay as they are
+        f64_file()
+    else:
+        main()

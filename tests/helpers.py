@@ -1,5 +1,6 @@
 """Shared fixture plumbing for the parity tests (weights are regenerated from seeds)."""
 import json
+import math
 import os
 
 import numpy as np
@@ -169,6 +170,100 @@ def stop_batch(fx, r, rows, tag=None):
         batch[k, :lens[k]] = fx[p + "ids"][i, :lens[k]]
     spk = fx[p + "spk"][rows] if p + "spk" in fx.files else None
     return batch, [int(x) for x in lens], steps, status, spk
+
+
+# ---- Tacotron (v1): the stop bias of a batch (tests/golden/make_tacotron1_golden.py) ----
+L06 = math.log(0.6 / 0.4)    # the stop rule's threshold sigmoid(logit) > 0.6, as a logit
+
+
+def choose_bias(raw, Ts, aligns, max_steps, min_token_stops, need_max_row, min_stop_step=3):
+    """Stop bias with the widest margin |l_t + b - logit(0.6)| over the tested steps (t > T/4, up to
+    each row's stop), such that at least min_token_stops rows stop by the token (not before
+    min_stop_step) and, if asked, a row runs max_steps + 1 steps."""
+    elig = [np.arange(len(l)) + 1 > T / 4 for l, T in zip(raw, Ts)]
+    cands = np.sort(np.concatenate([L06 - l[e] for l, e in zip(raw, elig)]))
+    best = None
+    for b in (cands[:-1] + cands[1:]) / 2:
+        margins, ntok, nmax, ok = [], 0, 0, True
+        for l, e, a, T in zip(raw, elig, aligns, Ts):
+            z = l + b - L06
+            by_align = e & (a[:len(l), T - 1] > 0.6)
+            idx_tok = np.nonzero(e & (z > 0))[0]
+            idx_al = np.nonzero(by_align)[0]
+            s_tok = idx_tok[0] if len(idx_tok) else len(l)
+            s_al = idx_al[0] if len(idx_al) else len(l)
+            end = min(s_tok, s_al, len(l) - 1)
+            if s_tok < s_al:
+                ntok += 1
+                ok &= s_tok + 1 >= min_stop_step
+            elif s_al == len(l) and len(l) == max_steps + 1:
+                nmax += 1
+            tested = e[:end + 1]
+            if tested.any():
+                margins.append(np.abs(z[:end + 1][tested]).min())
+        if not ok or ntok < min_token_stops or (need_max_row and nmax < 1):
+            continue
+        mm = min(margins)
+        if best is None or mm > best[1]:
+            best = (float(b), float(mm), ntok, nmax)
+    return best
+
+
+# ---- tacotron1_f64.npz: float64 arrays as fixed point in byte planes, so that they compress ----
+F64_BITS = 38  # stored values are multiples of 2^-38 (|x| < 2^25)
+
+
+def pack_f64(x):
+    """x (float64, any shape) -> uint8 (8, *x.shape): byte planes of round(x * 2^38) as little-endian int64."""
+    q = np.round(np.asarray(x, np.float64) * 2.0 ** F64_BITS).astype("<i8")
+    return np.ascontiguousarray(np.moveaxis(q[..., None].view(np.uint8), -1, 0))
+
+
+def unpack_f64(planes):
+    q = np.ascontiguousarray(np.moveaxis(np.asarray(planes, np.uint8), 0, -1)).view("<i8")[..., 0]
+    return q.astype(np.float64) / 2.0 ** F64_BITS
+
+
+_t1 = {}
+
+
+def taco1_f64():
+    """tacotron1_f64.npz, loaded once: (arrays by key, the new cases by tag)."""
+    if "f64" not in _t1:
+        fx = np.load(os.path.join(GOLDEN, "tacotron1_f64.npz"))
+        _t1["f64"] = (fx, {c["tag"]: c for c in json.loads(str(fx["cases"]))})
+    return _t1["f64"]
+
+
+def taco1_state_dict(cfg, seed, gains, stop_bias):
+    from tts_amd.spec import tacotron_spec
+    sd = synth_state_dict(tacotron_spec(cfg), seed, gains)
+    sd["decoder.stopnet.linear.bias"] = np.array([stop_bias], np.float32)
+    return sd
+
+
+def taco1_case(tag, **cfg_changes):
+    """(cfg, state dict, case record) of a new case of tacotron1_f64.npz; cfg_changes: e.g. another
+    postnet_output_dim on the same seed."""
+    from tts_amd.spec import TacotronV1Config
+    fx, cases = taco1_f64()
+    c = cases[tag]
+    cfg = TacotronV1Config(**dict(c["cfg"], **cfg_changes))
+    return cfg, taco1_state_dict(cfg, c["seed"], json.loads(str(fx["overrides"])), c["stop_bias"]), c
+
+
+def taco1_oracles(cfg, sd, hook=None):
+    """The float64 oracle and its float32 evaluation (the yardstick e32)."""
+    from oracle.tacotron1_np import Tacotron1Oracle
+    return Tacotron1Oracle(sd, cfg, hook=hook), Tacotron1Oracle(sd, cfg, np.float32)
+
+
+def build_taco1(cfg, sd, device="cuda"):
+    from tts_amd import Tacotron
+    m = Tacotron(num_chars=cfg.num_chars, num_speakers=0, r=cfg.r, postnet_output_dim=cfg.postnet_output_dim,
+                 attn_norm=cfg.attn_norm, memory_size=cfg.memory_size)
+    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
+    return m.to(device).eval()
 
 
 def melgan_state_dict(seed, cfg=None):
