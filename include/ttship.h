@@ -396,6 +396,53 @@ int tts_mag_to_feature(tts_ctx* ctx, const float* d_mag, const int32_t* h_lens, 
                        const float* d_offset, float clip_lo, float clip_hi, int use_clip, float* d_out,
                        void* stream);
 
+/* The waveform tail (wav_tail.hip): what lies between a model's output tensor and the bytes
+   Synthesizer.tts returns. The three entries only enqueue kernels on `stream`: ordinary launches,
+   every loop bounded by a length checked here on the host, plain vector stores, one fixed order of
+   operations per output, so row b of a batched call equals its own B = 1 call bit for bit.
+   1 <= B <= 64. An unsupported argument is an error that launches nothing.
+
+   tts_spec_to_mag <- AudioProcessor.inv_spectrogram's magnitudes (audio.py:232-236), the linear
+                      counterpart of tts_mel_to_linear without the basis:
+                      S = (10 ^ ((clip(x) * scale + offset) / spec_gain)) ^ power
+   d_spec      (B, M_max, n_freq) normalised linear spectrograms, frame-major (a Tacotron (v1)
+               postnet output); row b is read for t < h_lens[b] only (0 <= h_lens[b] <= M_max)
+   d_scale, d_offset (n_freq), clip_lo / clip_hi / use_clip: as tts_mel_to_linear
+   d_S         (B, M_max, n_freq); frames t >= h_lens[b] are written as zero
+   1 <= n_freq <= 1025. */
+int tts_spec_to_mag(tts_ctx* ctx, const float* d_spec, const int32_t* h_lens, int B, int M_max, int n_freq,
+                    const float* d_scale, const float* d_offset, float clip_lo, float clip_hi, int use_clip,
+                    float spec_gain, float power, float* d_S, void* stream);
+
+/* tts_deemphasis <- scipy.signal.lfilter([1], [1, -a], x) per row (audio.py:204-207):
+                     y[n] = x[n] + a * y[n-1], y[-1] = 0, for n < h_nsamples[b]
+   d_in, d_out (B, L_max); the rest of every output row is written as zero (0 <= h_nsamples[b] <=
+               L_max); d_out may be d_in
+   a           0 < a < 1
+   One workgroup per row scans the affine maps of 16-sample chunks, 512 chunks to a tile, the tiles
+   in sequence: the partition depends on the row's own length only. The powers of a that the scan
+   multiplies by are computed in double here and rounded once. */
+int tts_deemphasis(tts_ctx* ctx, const float* d_in, const int32_t* h_nsamples, int B, int L_max, double a,
+                   float* d_out, void* stream);
+
+/* tts_wav_finish <- the tail of Synthesizer.tts (server/synthesizer.py:179-193): per row
+                     AudioProcessor.find_endpoint (audio.py:302-309), the rows cut there and joined in
+                     order, `gap` zeros after each (the last included), then save_wav (audio.py:335-337)
+   d_wav       (B, L_max) waveforms, row b valid for h_nsamples[b] samples (0 <= h_nsamples[b] <= L_max)
+   window_length, hop_length, threshold: the endpoint of row b is x + hop_length for the first x in
+               range(hop_length, n - window_length, hop_length) whose window [x, x + window_length)
+               has a maximum of the signed samples m with (double) m < threshold, else n. Needs
+               1 <= hop_length <= window_length, window_length / hop_length <= 64.
+   d_pcm       int16, capacity sum(h_nsamples) + B * gap; the first *d_total entries are written:
+               trunc(x * f) in float32, f = (float) (32767 / (double) peak) when the float32 peak
+               of |x| over the joined signal is above 0.01, else 3276700: numpy 2's arithmetic in
+               save_wav on a float32 array, bit for bit
+   d_ends      (B) the endpoints; d_total: the joined length, sum(d_ends) + B * gap
+   0 <= gap < 2^24; the capacity must stay below 2^31. */
+int tts_wav_finish(tts_ctx* ctx, const float* d_wav, const int32_t* h_nsamples, int B, int L_max,
+                   int window_length, int hop_length, double threshold, int gap, int16_t* d_pcm, int32_t* d_ends,
+                   int32_t* d_total, void* stream);
+
 /* Measurement hook for bench.py: average device time (ms) of `iters` launches of one kernel of the
    last tts_taco_infer configuration, timed with hipEvents on the context's stream.
    which: 0 = decoder LSTM GEMM step kernel (K4), 1 = full decoder step (all 7 kernels). */

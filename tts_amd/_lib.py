@@ -110,6 +110,12 @@ SIGNATURES = [
     ("tts_mag_to_feature", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           _vp, ctypes.c_float, _vp, _vp, ctypes.c_float, ctypes.c_float, ctypes.c_int,
                                           _vp, _vp]),
+    ("tts_spec_to_mag", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp,
+                                       ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_float, ctypes.c_float,
+                                       _vp, _vp]),
+    ("tts_deemphasis", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, _vp, _vp]),
+    ("tts_wav_finish", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _vp]),
 ]
 
 
@@ -470,6 +476,32 @@ class Engine:
                                            None if basis is None else _ptr(basis), float(spec_gain), _ptr(scale),
                                            _ptr(offset), float(lo), float(hi), int(clip is not None), _ptr(out),
                                            _stream(mag.device)))
+
+    def spec_to_mag(self, spec, lens, scale, offset, clip, spec_gain, power, S):
+        """Normalised linear spectrograms (B, M, n_freq) -> magnitudes ``S``, the same shape
+        (tts_spec_to_mag); ``clip`` as in `mel_to_linear`."""
+        B, M, n_freq = spec.shape
+        lens_a, lens_p = _i32(lens)
+        lo, hi = (0.0, 0.0) if clip is None else clip
+        _check(self.lib.tts_spec_to_mag(self.h, _ptr(spec), lens_p, B, M, n_freq, _ptr(scale), _ptr(offset),
+                                        float(lo), float(hi), int(clip is not None), float(spec_gain), float(power),
+                                        _ptr(S), _stream(spec.device)))
+
+    def deemphasis(self, wav, nsamples, a, out):
+        """y[n] = x[n] + a y[n-1] on every row of ``wav`` (B, L_max) for ``nsamples[b]`` samples
+        (tts_deemphasis); ``out`` may be ``wav``, and is zero past each row's count."""
+        B, L = wav.shape
+        n_a, n_p = _i32(nsamples)
+        _check(self.lib.tts_deemphasis(self.h, _ptr(wav), n_p, B, L, float(a), _ptr(out), _stream(wav.device)))
+
+    def wav_finish(self, wav, nsamples, window_length, hop_length, threshold, gap, pcm, ends, total):
+        """Endpoints, join with gaps and 16-bit scaling of ``wav`` (B, L_max) (tts_wav_finish) into
+        the device tensors ``pcm`` (int16), ``ends`` (B int32) and ``total`` (one int32)."""
+        B, L = wav.shape
+        n_a, n_p = _i32(nsamples)
+        _check(self.lib.tts_wav_finish(self.h, _ptr(wav), n_p, B, L, int(window_length), int(hop_length),
+                                       float(threshold), int(gap), _ptr(pcm), _ptr(ends), _ptr(total),
+                                       _stream(wav.device)))
 
     def decoder_stats(self):
         """(path, [(ms, steps) per persistent launch]) of the last Tacotron2 decode."""

@@ -6,9 +6,10 @@ config's pad mode), trimming is librosa.effects.trim's frame-RMS rule. Mean-var 
 audio.py:80-86,108-186) reads compute_statistics.py's stats file through a restricted loader
 (`load_stats_file`). By default none of these touch the GPU; the audio-config key
 ``griffin_lim_device: "gpu"`` moves `inv_melspectrogram` onto the library's batched Griffin-Lim
-kernels (`inv_melspectrogram_batch`, fp32), and ``analysis_device: "gpu"`` moves `spectrogram` /
-`melspectrogram` onto its analysis kernels (`spectrogram_batch` / `melspectrogram_batch`, fp32);
-everything else stays on the host. Parity of the restated librosa pieces is unpinned
+kernels (`inv_melspectrogram_batch`, fp32), ``analysis_device: "gpu"`` moves `spectrogram` /
+`melspectrogram` onto its analysis kernels (`spectrogram_batch` / `melspectrogram_batch`, fp32), and
+``wav_tail_device: "gpu"`` lets `Synthesizer` run de-emphasis and the end of `tts()` (endpoints, join,
+16-bit scaling) on the device (`deemphasis_batch`, `finish_batch`); everything else stays on the host. Parity of the restated librosa pieces is unpinned
 (librosa is not importable here to make fixtures); tests check their defining properties.
 """
 import io
@@ -139,11 +140,13 @@ class AudioProcessor:
                  power=None, preemphasis=0.0, signal_norm=None, symmetric_norm=None, max_norm=None,
                  mel_fmin=None, mel_fmax=None, spec_gain=20, stft_pad_mode="reflect", clip_norm=True,
                  griffin_lim_iters=None, do_trim_silence=False, trim_db=60, stats_path=None, griffin_lim_device=None,
-                 analysis_device=None, **_):
+                 analysis_device=None, wav_tail_device=None, **_):
         if griffin_lim_device not in (None, "cpu", "gpu"):
             raise ValueError(f"griffin_lim_device must be 'cpu' or 'gpu', got {griffin_lim_device!r}")
         if analysis_device not in (None, "cpu", "gpu"):
             raise ValueError(f"analysis_device must be 'cpu' or 'gpu', got {analysis_device!r}")
+        if wav_tail_device not in (None, "cpu", "gpu"):
+            raise ValueError(f"wav_tail_device must be 'cpu' or 'gpu', got {wav_tail_device!r}")
         # None / "cpu": Griffin-Lim on the host (float64); "gpu": the library's batched kernels (fp32)
         self.griffin_lim_device = griffin_lim_device
         self._gl_dev_cache = {}
@@ -151,6 +154,9 @@ class AudioProcessor:
         # analysis kernels at B = 1 (fp32)
         self.analysis_device = analysis_device
         self._an_dev_cache = {}
+        # None / "cpu": Synthesizer de-emphasises, finds endpoints, joins and scales on the host;
+        # "gpu": on the device (`deemphasis_batch`, `finish_batch`). The methods here ignore it.
+        self.wav_tail_device = wav_tail_device
         self.sample_rate = sample_rate
         self.num_mels = num_mels
         self.min_level_db = min_level_db or 0
@@ -425,14 +431,16 @@ class AudioProcessor:
         return wav
 
     # -- batched Griffin-Lim on the GPU (tts_mel_to_linear + tts_griffin_lim)
-    def _denorm_affine(self):
+    def _denorm_affine(self, n_channels=None):
         """`_denormalize` on a mel as dB = clip(x) * scale + offset per channel: (scale, offset, clip)
-        with clip None or the (lo, hi) bounds."""
-        ones = np.ones(self.num_mels)
+        with clip None or the (lo, hi) bounds. With ``n_channels`` (a linear spectrogram's bins) the
+        mean-var scaler is picked as `_scaler_for` picks it, its refusals included."""
+        ones = np.ones(self.num_mels if n_channels is None else n_channels)
         if not self.signal_norm:
             return ones, 0.0 * ones, None
         if hasattr(self, "mel_scaler"):
-            return np.asarray(self.mel_scaler.scale_, np.float64), np.asarray(self.mel_scaler.mean_, np.float64), None
+            sc = self.mel_scaler if n_channels is None else self._scaler_for(np.empty((n_channels, 0)))
+            return np.asarray(sc.scale_, np.float64), np.asarray(sc.mean_, np.float64), None
         if self.symmetric_norm:
             scale = -self.min_level_db / (2 * self.max_norm)
             offset = self.max_norm * scale + self.min_level_db + self.ref_level_db
@@ -482,6 +490,81 @@ class AudioProcessor:
             eng.griffin_lim(S, lengths, self.fft_size, self.win_length, self.hop_length, self.griffin_lim_iters,
                             phase, wav)
         return wav, [self.hop_length * (n - 1) for n in lengths]
+
+    def inv_spectrogram_batch(self, specs, lengths, phase=None, deemphasis=True):
+        """`inv_spectrogram` of a batch on the GPU: ``specs`` (B, M_max, fft_size / 2 + 1) normalised
+        linear spectrograms on a ROCm device, frame-major (a Tacotron (v1) postnet output), row b valid
+        for ``lengths[b]`` frames; ``phase`` as in `inv_melspectrogram_batch`. The pre-emphasis
+        inverse runs on the device too unless ``deemphasis`` is False or `preemphasis` is 0. Returns
+        the (B, hop_length * (M_max - 1)) device tensor (rows zero past their own length) and the
+        per-row sample counts."""
+        from ._lib import get_engine
+        self._gl_check_params()
+        eng = get_engine(specs.device)
+        dev = specs.device
+        F = self.fft_size // 2 + 1
+        if specs.dim() != 3 or specs.shape[-1] != F:
+            raise ValueError(f"inv_spectrogram_batch: expected (B, M, {F}) spectrograms, got {tuple(specs.shape)}")
+        if (dev, "linear") not in self._gl_dev_cache:
+            scale, offset, clip = self._denorm_affine(F)
+            put = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)  # noqa: E731
+            self._gl_dev_cache[dev, "linear"] = (put(scale), put(offset), clip)
+        scale, offset, clip = self._gl_dev_cache[dev, "linear"]
+        specs = specs.contiguous().float()
+        B, M, _ = specs.shape
+        lengths = [int(n) for n in lengths]
+        S = torch.empty(B, M, F, device=dev)
+        if phase is None:
+            phase = torch.rand(B, M, F, device=dev)
+        phase = phase.contiguous().float()
+        assert phase.shape == S.shape and phase.device == dev
+        wav = torch.empty(B, self.hop_length * (M - 1), device=dev)
+        counts = [self.hop_length * (n - 1) for n in lengths]
+        with eng.lock:
+            eng.spec_to_mag(specs, lengths, scale, offset, clip, self.spec_gain, self.power, S)
+            eng.griffin_lim(S, lengths, self.fft_size, self.win_length, self.hop_length, self.griffin_lim_iters,
+                            phase, wav)
+            if deemphasis and self.preemphasis != 0:
+                eng.deemphasis(wav, counts, self.preemphasis, wav)
+        return wav, counts
+
+    # -- the waveform tail on the GPU (tts_deemphasis, tts_wav_finish)
+    def deemphasis_batch(self, wav, counts):
+        """The pre-emphasis inverse, ``scipy.signal.lfilter([1], [1, -preemphasis], row)``, on every
+        row of the (B, L_max) device tensor ``wav``, row b for ``counts[b]`` samples (fp32). Returns
+        a new tensor, zero past each row's count; with `preemphasis` 0 the filter is the identity."""
+        from ._lib import get_engine
+        eng = get_engine(wav.device)
+        wav = wav.contiguous().float()
+        counts = [int(n) for n in counts]
+        assert wav.dim() == 2 and len(counts) == wav.shape[0]
+        if self.preemphasis == 0:
+            return wav.clone()
+        out = torch.empty_like(wav)
+        with eng.lock:
+            eng.deemphasis(wav, counts, self.preemphasis, out)
+        return out
+
+    def finish_batch(self, wav, counts, gap=10000, threshold_db=-40, min_silence_sec=0.8):
+        """The end of `Synthesizer.tts` on the GPU: every row of the (B, L_max) device tensor ``wav``
+        (row b valid for ``counts[b]`` samples) is cut at its `find_endpoint`, the rows are joined in
+        order with ``gap`` zeros after each, and the result is scaled and truncated as `save_wav`
+        does. Returns the int16 numpy array `save_wav` would write and the list of endpoints."""
+        from ._lib import get_engine
+        eng = get_engine(wav.device)
+        wav = wav.contiguous().float()
+        counts = [int(n) for n in counts]
+        assert wav.dim() == 2 and len(counts) == wav.shape[0]
+        window_length = int(self.sample_rate * min_silence_sec)
+        hop_length = int(window_length / 4)
+        B = wav.shape[0]
+        pcm = torch.empty(max(1, sum(counts) + B * int(gap)), dtype=torch.int16, device=wav.device)
+        meta = torch.empty(B + 1, dtype=torch.int32, device=wav.device)  # the endpoints, then the total
+        with eng.lock:
+            eng.wav_finish(wav, counts, window_length, hop_length, float(self._db_to_amp(threshold_db)), gap, pcm,
+                           meta[:B], meta[B:])
+        meta = meta.cpu().tolist()
+        return pcm[:meta[B]].cpu().numpy(), meta[:B]
 
     # -- trimming / saving (audio.py:302-341)
     def find_endpoint(self, wav, threshold_db=-40, min_silence_sec=0.8):

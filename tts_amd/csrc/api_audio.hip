@@ -1,6 +1,7 @@
 // Audio post-processing entry points: mel -> linear magnitudes and batched Griffin-Lim
-// (griffin_lim.hip), and the analysis direction, waveform -> STFT magnitudes -> normalised features
-// (stft.hip). All of them only enqueue work: no host synchronisation, no graph capture.
+// (griffin_lim.hip), the waveform tail, linear spectrogram -> magnitudes, de-emphasis and the 16-bit
+// join (wav_tail.hip), and the analysis direction, waveform -> STFT magnitudes -> normalised
+// features (stft.hip). All of them only enqueue work: no host synchronisation, no graph capture.
 #include "host.h"
 
 #include <cmath>
@@ -176,6 +177,77 @@ int tts_griffin_lim(tts_ctx* c, const float* d_S, const int32_t* h_lens, int B, 
           std::swap(cur, nxt);
         }
         launch_gl_finish(cur, A.env.f(), d_wav, L, B, M_max, hop_length, wlo, whi, env_stride, c->s);
+      });
+}
+
+int tts_spec_to_mag(tts_ctx* c, const float* d_spec, const int32_t* h_lens, int B, int M_max, int n_freq,
+                    const float* d_scale, const float* d_offset, float clip_lo, float clip_hi, int use_clip,
+                    float spec_gain, float power, float* d_S, void* stream) {
+  return async_call(
+      c, stream,
+      [&] {
+        TTS_CHECK(d_spec && h_lens && d_scale && d_offset && d_S, "null argument");
+        TTS_CHECK(B >= 1 && B <= BMAX, "spec_to_mag: 1 <= B <= 64");
+        TTS_CHECK(n_freq >= 1 && n_freq <= 1025, "spec_to_mag: 1 <= n_freq <= 1025");
+        TTS_CHECK(M_max >= 1 && (long)M_max * n_freq < (1L << 30), "spec_to_mag: M_max out of range");
+        TTS_CHECK(spec_gain != 0.f, "spec_to_mag: spec_gain must not be 0");
+        check_rows(h_lens, B, 0, M_max, "spec_to_mag: h_lens[b] outside [0, M_max]");
+      },
+      [&] {
+        launch_spec_to_mag(d_spec, row_ints(h_lens, B), B, M_max, n_freq, d_scale, d_offset, clip_lo, clip_hi,
+                           use_clip, spec_gain, power, d_S, c->s);
+      });
+}
+
+int tts_deemphasis(tts_ctx* c, const float* d_in, const int32_t* h_nsamples, int B, int L_max, double a, float* d_out,
+                   void* stream) {
+  return async_call(
+      c, stream,
+      [&] {
+        TTS_CHECK(d_in && h_nsamples && d_out, "null argument");
+        TTS_CHECK(B >= 1 && B <= BMAX, "deemphasis: 1 <= B <= 64");
+        TTS_CHECK(a > 0.0 && a < 1.0, "deemphasis: the coefficient a must be in (0, 1)");
+        TTS_CHECK(L_max >= 1 && L_max < (1 << 30), "deemphasis: L_max out of range");
+        check_rows(h_nsamples, B, 0, L_max, "deemphasis: h_nsamples[b] outside [0, L_max]");
+      },
+      [&] {
+        DeemphTable tab;
+        for (int k = 0; k <= DE_C; ++k) tab.pw[k] = (float)std::pow(a, (double)k);
+        for (int s = 0; s < DE_LOG; ++s) tab.pwc[s] = (float)std::pow(a, (double)(DE_C << s));
+        launch_deemphasis(d_in, d_out, row_ints(h_nsamples, B), B, L_max, tab, c->s);
+      });
+}
+
+int tts_wav_finish(tts_ctx* c, const float* d_wav, const int32_t* h_nsamples, int B, int L_max, int window_length,
+                   int hop_length, double threshold, int gap, int16_t* d_pcm, int32_t* d_ends, int32_t* d_total,
+                   void* stream) {
+  return async_call(
+      c, stream,
+      [&] {
+        TTS_CHECK(d_wav && h_nsamples && d_pcm && d_ends && d_total, "null argument");
+        TTS_CHECK(B >= 1 && B <= BMAX, "wav_finish: 1 <= B <= 64");
+        TTS_CHECK(L_max >= 1 && L_max < (1 << 30), "wav_finish: L_max out of range");
+        TTS_CHECK(hop_length >= 1 && window_length >= hop_length && window_length / hop_length <= 64,
+                  "wav_finish: needs 1 <= hop_length <= window_length and window_length / hop_length <= 64");
+        TTS_CHECK(window_length < (1 << 30), "wav_finish: window_length out of range");
+        TTS_CHECK(!std::isnan(threshold), "wav_finish: threshold is NaN");
+        TTS_CHECK(gap >= 0 && gap < (1 << 24), "wav_finish: gap outside [0, 2^24)");
+        check_rows(h_nsamples, B, 0, L_max, "wav_finish: h_nsamples[b] outside [0, L_max]");
+        long cap = 0;
+        for (int b = 0; b < B; ++b) cap += (long)h_nsamples[b] + gap;
+        TTS_CHECK(cap < (1L << 31), "wav_finish: the joined signal would pass 2^31 samples");
+      },
+      [&] {
+        AudioWS& A = c->aws;
+        const int nblk = (L_max + hop_length - 1) / hop_length;
+        const size_t maxima = (size_t)B * nblk;
+        A.tail.ensure((2 * maxima + BMAX + 1) * sizeof(float));
+        float* smax = A.tail.f();
+        float* amax = smax + maxima;
+        int* offs = reinterpret_cast<int*>(amax + maxima);
+        float* factor = reinterpret_cast<float*>(offs + BMAX);
+        launch_wav_finish(d_wav, row_ints(h_nsamples, B), B, L_max, window_length, hop_length, threshold, gap, smax,
+                          amax, nblk, offs, factor, d_pcm, d_ends, d_total, c->s);
       });
 }
 

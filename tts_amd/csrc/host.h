@@ -414,6 +414,8 @@ struct AudioWS {
   // analysis (stft.hip): twiddles e^{-2 pi i m / n_fft} and the window of the last tts_stft_mag call
   DevBuf sW, swin;
   int s_nfft = -1, s_win = -1;
+  // tts_wav_finish (wav_tail.hip): hop-block maxima, row offsets and the scale factor
+  DevBuf tail;
 };
 
 // one submitted fused call: what its fp32 re-run needs if the split-f16 vocoder raised the range

@@ -156,6 +156,26 @@ void launch_mel_to_linear(const float* mel, const RowInts& lens, int B, int M_ma
                           const float* scale, const float* offset, float clip_lo, float clip_hi, int use_clip,
                           float spec_gain, float power, float* S, hipStream_t s);
 
+// wav_tail.hip. x (B, M_max, F) normalised linear spectrograms -> S, the same shape
+void launch_spec_to_mag(const float* x, const RowInts& lens, int B, int M_max, int F, const float* scale,
+                        const float* offset, float clip_lo, float clip_hi, int use_clip, float spec_gain, float power,
+                        float* S, hipStream_t s);
+// de-emphasis: a workgroup of DE_T threads per row, each thread DE_C samples of a tile. The powers
+// of the coefficient the kernel multiplies by, rounded from double: pw[k] = a^k and
+// pwc[s] = a^(DE_C 2^s)
+constexpr int DE_T = 512, DE_C = 16, DE_LOG = 9;  // DE_T == 1 << DE_LOG
+struct DeemphTable {
+  float pw[DE_C + 1];
+  float pwc[DE_LOG];
+};
+void launch_deemphasis(const float* in, float* out, const RowInts& ns, int B, int L_max, const DeemphTable& tab,
+                       hipStream_t s);
+// the four launches of tts_wav_finish; smax, amax (B, nblk) hop-block maxima with nblk >=
+// ceil(L_max / hop), offs (B) and factor (1) scratch
+void launch_wav_finish(const float* wav, const RowInts& ns, int B, int L_max, int window, int hop, double thr, int gap,
+                       float* smax, float* amax, int nblk, int* offs, float* factor, int16_t* pcm, int* ends,
+                       int* total, hipStream_t s);
+
 // stft.hip. nsamp holds the rows' sample counts (by value, as above); W = e^{-2 pi i m / n_fft}
 // (n_fft complex), win = the window zero-padded to n_fft, nonzero inside [wlo, whi). fft: the
 // 1024-point FFT kernel (n_fft must be 1024), else the direct DFT. out (B, M_max, n_fft / 2 + 1).

@@ -7,6 +7,9 @@ Follows `TTS/server/synthesizer.py:21-193`. What differs on purpose:
     own mel length, so every sentence equals its B=1 synthesis;
   * without a vocoder checkpoint the Griffin-Lim fallback runs on the CPU (`tts_amd.audio`), or, with
     ``"griffin_lim_device": "gpu"`` in the audio config, batched on the GPU from the postnet output;
+  * with ``"wav_tail_device": "gpu"`` in the audio config, `tts()` leaves waveforms made on the
+    device there and cuts, joins and scales them in one `AudioProcessor.finish_batch` call (the same
+    bytes), and the Griffin-Lim branches de-emphasise on the device;
   * checkpoints load with `torch.load(..., weights_only=True)`;
   * sentence splitting and the text front end are the stand-ins of `tts_amd.text` (pysbd,
     phonemizer, unidecode and inflect are not in this image); phoneme configs need a
@@ -17,11 +20,13 @@ Follows `TTS/server/synthesizer.py:21-193`. What differs on purpose:
     sentence order. The workers start before this process touches the GPU.
 """
 import functools
+import io
 import json
 import os
 import time
 
 import numpy as np
+import scipy.io.wavfile
 import torch
 
 from .audio import AudioProcessor, wav_bytes
@@ -128,17 +133,25 @@ class Synthesizer:
     def split_into_sentences(text):
         return split_into_sentences(text)
 
-    def synthesize_batch(self, sentences, speaker_id=None):
-        """Sentences -> list of per-sentence waveforms (float32 numpy), one GPU call per model (per
-        GPU when sharded over a pool)."""
-        seqs = [text_to_seqvec(s, self.tts_config, self.phonemize) for s in sentences]
-        if self.pool is not None:
-            return self.pool.map(list(sentences), costs=[len(q) for q in seqs], speaker_id=speaker_id)
+    def _host_deemphasis(self, rows):
+        """scipy's lfilter per row, as `AudioProcessor.inv_melspectrogram` applies it (float32 out)."""
+        import scipy.signal
+        return [scipy.signal.lfilter([1], [1, -self.ap.preemphasis], w).astype(np.float32) for w in rows]
+
+    def _synthesize(self, seqs, speaker_id, on_device):
+        """One batched call per model on the token rows ``seqs``: the list of per-sentence float32
+        numpy waveforms. With ``on_device`` (`tts()` under ``wav_tail_device == "gpu"``), waveforms
+        made on the device (vocoder, fused MB-MelGAN call, GPU Griffin-Lim) stay there:
+        ``(wav, counts)``, the (B, L_max) device tensor and the per-row sample counts."""
         lens = [max(1, len(q)) for q in seqs]
         dev = "cuda" if self.use_cuda else "cpu"
         batch = np.zeros((len(seqs), max(lens)), np.int64)
         for i, q in enumerate(seqs):
             batch[i, :len(q)] = q
+        gl_gpu = self.ap.griffin_lim_device == "gpu"
+        # the pre-emphasis inverse after a GPU Griffin-Lim: on the device, or scipy's lfilter per row
+        tail_gpu = self.ap.wav_tail_device == "gpu"
+        deemph_host = self.ap.preemphasis != 0 and not tail_gpu
         with torch.no_grad():
             wav = None
             if isinstance(self.tts_model, GlowTts):  # synthesis.py:60-66
@@ -155,6 +168,14 @@ class Synthesizer:
                         raise ValueError("a Tacotron (v1) model outputs linear spectrograms; the vocoders take mels")
                     _, post, _, _ = self.tts_model.inference(ids, text_lengths=lens)
                     mel_lens = [int(m) for m in self.tts_model.last_mel_lengths]
+                    if gl_gpu:
+                        # one batched call on the postnet rows where they lie, phases drawn on the device
+                        wav, counts = self.ap.inv_spectrogram_batch(post, mel_lens, deemphasis=tail_gpu)
+                        if on_device:
+                            return wav, counts
+                        wav = wav.cpu().numpy()
+                        rows = [wav[i, :n] for i, n in enumerate(counts)]
+                        return self._host_deemphasis(rows) if deemph_host else rows
                     post = post.cpu().numpy()
                     return [self.ap.inv_spectrogram(post[i, :mel_lens[i]].T).astype(np.float32)
                             for i in range(len(seqs))]
@@ -169,33 +190,59 @@ class Synthesizer:
                 if wav is None:
                     wav = self.vocoder_model.inference(post.transpose(1, 2), lengths=mel_lens)
                 hop = wav.shape[-1] // post.shape[1]
-                wav = wav.reshape(len(seqs), -1).cpu().numpy()
+                wav = wav.reshape(len(seqs), -1)
+                if on_device:
+                    return wav, [n * hop for n in mel_lens]
+                wav = wav.cpu().numpy()
                 return [wav[i, :mel_lens[i] * hop] for i in range(len(seqs))]
-            if self.ap.griffin_lim_device == "gpu":
+            if gl_gpu:
                 # Griffin-Lim on the device, on the postnet rows in place (no host copy of the mels)
                 wav, counts = self.ap.inv_melspectrogram_batch(post, mel_lens)
+                if self.ap.preemphasis != 0 and tail_gpu:
+                    wav = self.ap.deemphasis_batch(wav, counts)
+                if on_device:
+                    return wav, counts
                 wav = wav.cpu().numpy()
-                if self.ap.preemphasis != 0:
-                    import scipy.signal
-                    return [scipy.signal.lfilter([1], [1, -self.ap.preemphasis], wav[i, :n]).astype(np.float32)
-                            for i, n in enumerate(counts)]
-                return [wav[i, :n] for i, n in enumerate(counts)]
+                rows = [wav[i, :n] for i, n in enumerate(counts)]
+                return self._host_deemphasis(rows) if deemph_host else rows
         post = post.cpu().numpy()
         return [self.ap.inv_melspectrogram(post[i, :mel_lens[i]].T).astype(np.float32) for i in range(len(seqs))]
 
+    def synthesize_batch(self, sentences, speaker_id=None):
+        """Sentences -> list of per-sentence waveforms (float32 numpy), one GPU call per model (per
+        GPU when sharded over a pool)."""
+        seqs = [text_to_seqvec(s, self.tts_config, self.phonemize) for s in sentences]
+        if self.pool is not None:
+            return self.pool.map(list(sentences), costs=[len(q) for q in seqs], speaker_id=speaker_id)
+        return self._synthesize(seqs, speaker_id, on_device=False)
+
     def tts(self, text, speaker_id=None):
-        """synthesizer.py:134-193"""
+        """synthesizer.py:134-193. With ``"wav_tail_device": "gpu"`` in the audio config (and no
+        pool) waveforms made on the device stay there: endpoints, the join and the 16-bit scaling
+        are one `AudioProcessor.finish_batch` call, and only the int16 samples come to the host."""
         start_time = time.time()
         sens = self.split_into_sentences(text)
         print(sens)
-        wavs = []
-        for wav in self.synthesize_batch(sens, speaker_id):
-            wav = wav[:self.ap.find_endpoint(wav)]  # synthesis.py:130-131
-            wavs += list(wav)
-            wavs += [0] * 10000
-        out = wav_bytes(self.ap, np.asarray(wavs, np.float32))
+        if self.pool is None and self.ap.wav_tail_device == "gpu":
+            seqs = [text_to_seqvec(s, self.tts_config, self.phonemize) for s in sens]
+            rows = self._synthesize(seqs, speaker_id, on_device=True)
+        else:
+            rows = self.synthesize_batch(sens, speaker_id)
+        if isinstance(rows, tuple):  # (wav, counts) on the device
+            pcm, _ = self.ap.finish_batch(*rows)
+            out = io.BytesIO()
+            scipy.io.wavfile.write(out, self.ap.sample_rate, pcm)
+            n_samples = len(pcm)
+        else:
+            wavs = []
+            for wav in rows:
+                wav = wav[:self.ap.find_endpoint(wav)]  # synthesis.py:130-131
+                wavs += list(wav)
+                wavs += [0] * 10000
+            out = wav_bytes(self.ap, np.asarray(wavs, np.float32))
+            n_samples = len(wavs)
         process_time = time.time() - start_time
-        audio_time = len(wavs) / self.tts_config["audio"]["sample_rate"]
+        audio_time = n_samples / self.tts_config["audio"]["sample_rate"]
         print(f" > Processing time: {process_time}")
         print(f" > Real-time factor: {process_time / audio_time}")
         return out
