@@ -502,6 +502,46 @@ int tts_taco_mbmelgan_finish(tts_ctx* ctx, int64_t ticket, void* stream);
    Tacotron2 call reports the encoder barrier error; -1 turns it off. Only tests call it. */
 int tts_test_stall_lstm(int recurrence);
 
+/* Test hook: one launch of the generic conv (conv.hip / conv_x3.hip) through the production path.
+   The layer is packed from the host weight and bias with the loaders' own functions (pack_conv,
+   or pack_convT for a ConvTranspose1d), one run_conv is issued on the context's stream, the stream
+   is synchronised and the layer is freed. The context's GEMM mode (tts_set_gemm_mode) decides
+   whether the split-f16 kernel is offered; the range flag is reported, no fp32 re-run is made.
+   Strides are {batch, channel, time} in elements. Only tests and tools call it.
+     transposed = 0: Conv1d, h_weight (Cout, Cin, K), `nphase` phase blocks of it when nphase > 1
+                     (each with its pad_left[phase]; output position q * out_mul + phase);
+     transposed = 1: ConvTranspose1d(k = 2u, stride u, padding u / 2), u = nphase, h_weight
+                     (Cin, Cout, 2u); K, dil and pad_left are ignored. merged_u = 0 runs the u
+                     polyphase convs (set out_mul = u), merged_u = u the phase-merged split-f16 form
+                     (set out_mul = 1 and max_q = the longest row + 1).
+   Every other field has the meaning of the same-named ConvCall / ConvArgs field (csrc/common.h).
+   Out: ran_x3 (1 split-f16 kernel, 0 fp32 kernel), tq (tile width in output positions of the kernel
+   launched), range_flag (the split-f16 range flag after the call; 0 on the fp32 kernel). */
+typedef struct tts_conv_test {
+  const float* h_weight;
+  const float* h_bias; /* [Cout] */
+  int32_t transposed, Cin, Cout, K, dil, nphase;
+  int32_t pad_left[8];
+  int32_t merged_u;
+  int32_t nsrc; /* 1 or 2 */
+  const float* d_src[2];
+  int64_t src_strides[2][3];
+  int32_t src_C[2];   /* channels of each source (nsrc = 2; one source has Cin) */
+  int32_t src_act[2]; /* 1: leaky-relu(0.2) on load */
+  float* d_out;
+  int64_t out_strides[3];
+  const float* d_resid; /* or NULL */
+  int64_t resid_strides[3];
+  int32_t resid_rows;
+  const float* d_aux; /* or NULL */
+  int64_t auxb;
+  const int32_t* h_lens; /* [B], host */
+  int32_t B, max_q, len_add, in_mul, q_mul, out_mul, rep_pad, pad_mode, epi;
+  int32_t ran_x3, tq; /* out */
+  uint32_t range_flag; /* out */
+} tts_conv_test;
+int tts_test_conv(tts_ctx* ctx, tts_conv_test* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -99,6 +99,7 @@ SIGNATURES = [
     ("tts_decoder_stats", ctypes.c_int, [_vp, _c_i_p, _c_i_p, _c_f_p, _c_i_p]),
     ("tts_set_gemm_mode", ctypes.c_int, [_vp, ctypes.c_int]),
     ("tts_test_stall_lstm", ctypes.c_int, [ctypes.c_int]),
+    ("tts_test_conv", ctypes.c_int, [_vp, _vp, _vp]),
     ("tts_gemm_mode", ctypes.c_int, [_vp, _c_i_p, _c_i64_p]),
     ("tts_mel_to_linear", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          _vp, _vp, _vp, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_float,
@@ -117,6 +118,28 @@ SIGNATURES = [
     ("tts_wav_finish", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _vp]),
 ]
+
+
+class ConvTest(ctypes.Structure):
+    """``tts_conv_test`` of include/ttship.h (the descriptor of tts_test_conv)."""
+    _fields_ = [
+        ("h_weight", _vp), ("h_bias", _vp),
+        ("transposed", ctypes.c_int32), ("Cin", ctypes.c_int32), ("Cout", ctypes.c_int32), ("K", ctypes.c_int32),
+        ("dil", ctypes.c_int32), ("nphase", ctypes.c_int32),
+        ("pad_left", ctypes.c_int32 * 8),
+        ("merged_u", ctypes.c_int32), ("nsrc", ctypes.c_int32),
+        ("d_src", _vp * 2),
+        ("src_strides", (ctypes.c_int64 * 3) * 2),
+        ("src_C", ctypes.c_int32 * 2), ("src_act", ctypes.c_int32 * 2),
+        ("d_out", _vp), ("out_strides", ctypes.c_int64 * 3),
+        ("d_resid", _vp), ("resid_strides", ctypes.c_int64 * 3), ("resid_rows", ctypes.c_int32),
+        ("d_aux", _vp), ("auxb", ctypes.c_int64),
+        ("h_lens", _vp),
+        ("B", ctypes.c_int32), ("max_q", ctypes.c_int32), ("len_add", ctypes.c_int32), ("in_mul", ctypes.c_int32),
+        ("q_mul", ctypes.c_int32), ("out_mul", ctypes.c_int32), ("rep_pad", ctypes.c_int32),
+        ("pad_mode", ctypes.c_int32), ("epi", ctypes.c_int32),
+        ("ran_x3", ctypes.c_int32), ("tq", ctypes.c_int32), ("range_flag", ctypes.c_uint32),
+    ]
 
 
 def load_library():
@@ -502,6 +525,48 @@ class Engine:
         _check(self.lib.tts_wav_finish(self.h, _ptr(wav), n_p, B, L, int(window_length), int(hop_length),
                                        float(threshold), int(gap), _ptr(pcm), _ptr(ends), _ptr(total),
                                        _stream(wav.device)))
+
+    def conv_test(self, weight, bias, lens, src, out, max_q, device, transposed=False, K=1, dil=1, nphase=1,
+                  pad_left=(0,), merged_u=0, src2=None, resid=None, resid_rows=0, aux=None, auxb=0, len_add=0,
+                  in_mul=1, q_mul=1, out_mul=1, rep_pad=0, pad_mode=0, epi=0):
+        """One generic conv launch through pack_conv / run_conv (tts_test_conv; tests and tools).
+        ``weight``: numpy (Cout, Cin, K), (nphase, Cout, Cin, K), or (Cin, Cout, 2 nphase) when
+        ``transposed``; ``src`` / ``src2``: (device address, (sb, sc, st), channels, act); ``out`` /
+        ``resid``: (device address, (sb, sc, st)); ``aux``: device address. Returns (ran_x3, tq,
+        range_flag)."""
+        w = np.ascontiguousarray(weight, dtype=np.float32)
+        b = np.ascontiguousarray(bias, dtype=np.float32)
+        lens_a = np.ascontiguousarray(lens, dtype=np.int32)
+        d = ConvTest()
+        d.h_weight, d.h_bias, d.h_lens = w.ctypes.data, b.ctypes.data, lens_a.ctypes.data
+        d.transposed = int(bool(transposed))
+        if transposed:
+            d.Cin, d.Cout = w.shape[0], w.shape[1]
+        else:
+            d.Cout, d.Cin = w.shape[-3], w.shape[-2]
+        assert len(b) == d.Cout
+        d.K, d.dil, d.nphase, d.merged_u = K, dil, nphase, merged_u
+        for i, p in enumerate(pad_left):
+            d.pad_left[i] = p
+        d.nsrc = 1 if src2 is None else 2
+        for i, s in enumerate((src,) if src2 is None else (src, src2)):
+            d.d_src[i] = s[0]
+            for j in range(3):
+                d.src_strides[i][j] = s[1][j]
+            d.src_C[i], d.src_act[i] = s[2], s[3]
+        d.d_out = out[0]
+        for j in range(3):
+            d.out_strides[j] = out[1][j]
+        if resid is not None:
+            d.d_resid = resid[0]
+            for j in range(3):
+                d.resid_strides[j] = resid[1][j]
+        d.resid_rows, d.d_aux, d.auxb = resid_rows, aux, auxb
+        d.B, d.max_q, d.len_add, d.in_mul, d.q_mul, d.out_mul = len(lens_a), max_q, len_add, in_mul, q_mul, out_mul
+        d.rep_pad, d.pad_mode, d.epi = rep_pad, pad_mode, epi
+        with self.lock:
+            _check(self.lib.tts_test_conv(self.h, ctypes.c_void_p(ctypes.addressof(d)), _stream(device)))
+        return bool(d.ran_x3), int(d.tq), int(d.range_flag)
 
     def decoder_stats(self):
         """(path, [(ms, steps) per persistent launch]) of the last Tacotron2 decode."""

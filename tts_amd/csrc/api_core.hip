@@ -155,7 +155,38 @@ void pack_conv_x3_only(ConvLayer& L, const std::vector<float>& Wm, const std::ve
   L.bias.upload(bias);
 }
 
-void run_conv(const ConvLayer& L, const ConvCall& c, hipStream_t st) {
+void pack_convT(ConvLayer& L, ConvLayer& Lm, const std::vector<float>& wt, const std::vector<float>& bias, int u,
+                int Cin, int Cout) {
+  TTS_CHECK(u % 2 == 0 && u >= 2 && u <= 8, "upsample factors must be even and <= 8");
+  TTS_CHECK(wt.size() == (size_t)Cin * Cout * 2 * u && bias.size() == (size_t)Cout, "ConvTranspose weight / bias size");
+  const int p = u / 2;
+  std::vector<float> Wm((size_t)u * Cout * Cin * 2);
+  int pls[8] = {0};
+  for (int ph = 0; ph < u; ++ph) {
+    const int dmax = (ph + p) / u, dmin = dmax - 1;
+    pls[ph] = -dmin;
+    for (int co = 0; co < Cout; ++co)
+      for (int ci = 0; ci < Cin; ++ci)
+        for (int jj = 0; jj < 2; ++jj) {
+          const int delta = dmin + jj;
+          const int k = ph + p - delta * u;
+          Wm[(((size_t)ph * Cout + co) * Cin + ci) * 2 + jj] = wt[((size_t)ci * Cout + co) * (2 * u) + k];
+        }
+  }
+  pack_conv(L, Wm, bias, Cin, Cout, 2, 1, u, pls);
+  bool wm_in_range = true;
+  for (float v : Wm) wm_in_range &= std::fabs(v) < F16_RANGE;
+  // the merged GEMM has u * Cout rows, so it is covered even where Cout alone is not (full-band 64 -> 32)
+  if (wm_in_range && conv_x3_supported(Cin, u * Cout, 2, 1)) {
+    std::vector<float> bm((size_t)u * Cout);
+    for (size_t r = 0; r < bm.size(); ++r) bm[r] = bias[r / u];
+    pack_conv_x3_only(Lm, merge_convT_phases(Wm, u, Cin, Cout), bm, Cin, u * Cout, 2);
+  } else {
+    Lm.W16.reset();
+  }
+}
+
+ConvRan run_conv(const ConvLayer& L, const ConvCall& c, hipStream_t st) {
   ConvArgs a{};
   a.src[0] = c.s[0];
   a.src[1] = c.nsrc > 1 ? c.s[1] : c.s[0];
@@ -198,10 +229,9 @@ void run_conv(const ConvLayer& L, const ConvCall& c, hipStream_t st) {
     a.W16 = L.W16.p;
     a.w16_phase_stride = L.w16_stride;
     a.oflow = c.oflow;
-    launch_conv_x3(a, st);
-    return;
+    return {true, launch_conv_x3(a, st)};
   }
-  launch_conv(a, L.tile, st);
+  return {false, launch_conv(a, L.tile, st)};
 }
 
 void enter(tts_ctx* c, void* stream, bool join_voc) {
@@ -353,6 +383,69 @@ int tts_set_gemm_mode(tts_ctx* c, int mode) {
 int tts_test_stall_lstm(int recurrence) {
   g_test_stall_lstm.store(recurrence < 0 ? -1 : recurrence);
   return 0;
+}
+
+int tts_test_conv(tts_ctx* c, tts_conv_test* d, void* stream) {
+  return guarded_ctx(c, [&] {
+    TTS_CHECK(d && d->h_weight && d->h_bias && d->h_lens && d->d_src[0] && d->d_out, "test_conv: null argument");
+    TTS_CHECK(d->Cin >= 1 && d->Cout >= 1 && d->B >= 1 && d->max_q >= 0, "test_conv: sizes");
+    TTS_CHECK(d->nsrc == 1 || (d->nsrc == 2 && d->d_src[1] && d->src_C[0] + d->src_C[1] == d->Cin), "test_conv: sources");
+    TTS_CHECK(d->nphase >= 1 && d->nphase <= 8, "conv: nphase");
+    auto lay = [](const int64_t* s) {
+      TTS_CHECK(s[1] >= 0 && s[2] >= 0 && s[1] < (1L << 31) && s[2] < (1L << 31), "test_conv: strides");
+      return Layout{(long)s[0], (int)s[1], (int)s[2]};
+    };
+    d->ran_x3 = d->tq = 0;
+    d->range_flag = 0;
+    DeviceGuard g(c->device);
+    enter(c, stream);
+    ConvLayer L, Lm;
+    const std::vector<float> bias(d->h_bias, d->h_bias + d->Cout);
+    if (d->transposed) {
+      const int u = d->nphase;
+      TTS_CHECK(d->merged_u == 0 || d->merged_u == u, "test_conv: merged_u is 0 or the stride");
+      pack_convT(L, Lm, std::vector<float>(d->h_weight, d->h_weight + (size_t)d->Cin * d->Cout * 2 * u), bias, u,
+                 d->Cin, d->Cout);
+    } else {
+      TTS_CHECK(d->K >= 1 && d->dil >= 1 && d->merged_u == 0, "test_conv: taps");
+      const size_t n = (size_t)d->nphase * d->Cout * d->Cin * d->K;
+      pack_conv(L, std::vector<float>(d->h_weight, d->h_weight + n), bias, d->Cin, d->Cout, d->K, d->dil, d->nphase,
+                d->pad_left);
+    }
+    DevBuf lens;
+    ConvCall cc = conv_call(c, put_rows(lens, d->h_lens, d->B, c->s), d->B, d->max_q);
+    cc.in(d->d_src[0], lay(d->src_strides[0]), d->nsrc == 2 ? d->src_C[0] : d->Cin, d->src_act[0]);
+    if (d->nsrc == 2) {
+      cc.in2(d->d_src[1], lay(d->src_strides[1]), d->src_C[1]);
+      cc.s[1].act = d->src_act[1];
+    }
+    cc.to(d->d_out, lay(d->out_strides));
+    if (d->d_resid) cc.add(d->d_resid, lay(d->resid_strides));
+    cc.resid_rows = d->resid_rows;
+    cc.aux = d->d_aux;
+    cc.auxb = (long)d->auxb;
+    cc.pad_mode = d->pad_mode;
+    cc.len_add = d->len_add;
+    cc.in_mul = d->in_mul;
+    cc.q_mul = d->q_mul;
+    cc.out_mul = d->out_mul;
+    cc.rep_pad = d->rep_pad;
+    cc.epi = d->epi;
+    cc.merged_u = d->merged_u;
+    if (cc.oflow) HIP_OK(hipMemsetAsync(cc.oflow, 0, 4, c->s));
+    // the layers' buffers are freed when this scope ends: wait for the launch first, also on an error
+    struct Sync {
+      hipStream_t s;
+      ~Sync() { (void)hipStreamSynchronize(s); }
+    } sync{c->s};
+    const ConvRan ran = run_conv(d->merged_u ? Lm : L, cc, c->s);
+    d->ran_x3 = ran.x3 ? 1 : 0;
+    d->tq = ran.tq;
+    if (cc.oflow) HIP_OK(hipMemcpyAsync(&c->pinned[PIN_FLAG], cc.oflow, 4, hipMemcpyDeviceToHost, c->s));
+    HIP_OK(hipStreamSynchronize(c->s));
+    if (cc.oflow) d->range_flag = (uint32_t)c->pinned[PIN_FLAG];
+    leave(c, stream);
+  });
 }
 
 int tts_gemm_mode(tts_ctx* c, int* mode, int64_t* fallbacks) {

@@ -45,32 +45,9 @@ static void melgan_finalize(tts_ctx* c, int in_ch, int out_ch, int base, const i
     const int u = ups[i];
     TTS_CHECK(u % 2 == 0 && u <= 8, "upsample factors must be even and <= 8");
     const int cin = base >> i, cout = base >> (i + 1);
-    const int p = u / 2;
     const std::string nm = "layers." + std::to_string(idx + 1);
     auto wt = wn_weight(m, nm, {cin, cout, 2 * u});  // ConvTranspose1d weight (Cin, Cout, K)
-    std::vector<float> Wm((size_t)u * cout * cin * 2);
-    int pls[8] = {0};
-    for (int ph = 0; ph < u; ++ph) {
-      const int dmax = (ph + p) / u, dmin = dmax - 1;
-      pls[ph] = -dmin;
-      for (int co = 0; co < cout; ++co)
-        for (int ci = 0; ci < cin; ++ci)
-          for (int jj = 0; jj < 2; ++jj) {
-            const int delta = dmin + jj;
-            const int k = ph + p - delta * u;
-            Wm[(((size_t)ph * cout + co) * cin + ci) * 2 + jj] = wt[((size_t)ci * cout + co) * (2 * u) + k];
-          }
-    }
-    pack_conv(G.convT[i], Wm, need(m, nm + ".bias", {cout}).d, cin, cout, 2, 1, u, pls);
-    bool wm_in_range = true;
-    for (float v : Wm) wm_in_range &= std::fabs(v) < F16_RANGE;
-    // the merged GEMM has u * cout rows, so it is covered even where cout alone is not (full-band 64 -> 32)
-    if (wm_in_range && conv_x3_supported(cin, u * cout, 2, 1)) {
-      const auto& bias = need(m, nm + ".bias", {cout}).d;
-      std::vector<float> bm((size_t)u * cout);
-      for (size_t r = 0; r < bm.size(); ++r) bm[r] = bias[r / u];
-      pack_conv_x3_only(G.convTm[i], merge_convT_phases(Wm, u, cin, cout), bm, cin, u * cout, 2);
-    }
+    pack_convT(G.convT[i], G.convTm[i], wt, need(m, nm + ".bias", {cout}).d, u, cin, cout);
     C = cout;
     for (int bk = 0; bk < nres; ++bk) {
       const int d = 1;

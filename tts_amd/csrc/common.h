@@ -160,10 +160,11 @@ struct ConvArgs {
 enum ConvTile { TILE_128x64 = 0, TILE_64x64, TILE_192x64, TILE_96x64, TILE_48x128, TILE_80x64, TILE_16x256 };
 int conv_tile_tc(int tile);
 int conv_tile_for_cout(int cout);
-void launch_conv(const ConvArgs& a, int tile, hipStream_t s);
+// both launchers return the tile width TQ of the kernel they launched (0: nothing to launch)
+int launch_conv(const ConvArgs& a, int tile, hipStream_t s);
 // split-f16 form of the same conv (conv_x3.hip); false when the shape is not covered
 bool conv_x3_supported(int Cin, int Cout, int K, int dil);
-void launch_conv_x3(const ConvArgs& a, hipStream_t s);
+int launch_conv_x3(const ConvArgs& a, hipStream_t s);
 // host packing of the split weights: Wm = nphase blocks of [Cout][Cin*K] row-major
 std::vector<uint16_t> pack_conv_x3(const std::vector<float>& Wm, int Cin, int Cout, int K, int nphase,
                                    long* phase_stride_bytes);

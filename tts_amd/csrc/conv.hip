@@ -231,12 +231,12 @@ int conv_tile_for_cout(int cout) {
   return TILE_16x256;
 }
 
-void launch_conv(const ConvArgs& a, int tile, hipStream_t s) {
+int launch_conv(const ConvArgs& a, int tile, hipStream_t s) {
   TTS_CHECK(a.Cin % 16 == 0, "conv: Cin must be a multiple of 16");
   TTS_CHECK(a.Cout_pad % conv_tile_tc(tile) == 0, "conv: Cout_pad / tile mismatch");
   TTS_CHECK(a.nphase >= 1 && a.nphase <= 8, "conv: nphase");
   TTS_CHECK((a.K - 1) * a.dil <= CONV_MAX_SPAN, "conv: receptive span too large for the generic kernel");
-  if (a.max_q <= 0 || a.B <= 0) return;
+  if (a.max_q <= 0 || a.B <= 0) return 0;
   int TQ = conv_tile_tq(tile), TC = conv_tile_tc(tile);
   // compile-time-tap variants with a weight ring (tools/conv_bench.hip, postnet 512->512 k5:
   // 128x64 one-ahead 642 us, 64x64 ring5 557 us)
@@ -264,6 +264,7 @@ void launch_conv(const ConvArgs& a, int tile, hipStream_t s) {
       }
   }
   HIP_OK(hipGetLastError());
+  return TQ;
 }
 
 void swizzle_rows16(const float* Wm, int rows, int rows_pad, int Kdim, float* dst) {

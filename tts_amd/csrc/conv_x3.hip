@@ -138,7 +138,8 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_x3_kernel(ConvArgs a, int n
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
           v[c] = keep ? sr[j][c] : 0.f;
-          mx = fmaxf(mx, __builtin_fabsf(v[c]));
+          // IEEE-754 maximum (v_maximum3_f32): keeps a NaN, which fmaxf would drop
+          mx = __builtin_elementwise_maximum(mx, __builtin_fabsf(v[c]));
           if (act) v[c] = lrelu02(v[c]);
         }
         bad |= !(mx < F16_RANGE);  // |lrelu(v)| <= |v|
@@ -350,7 +351,7 @@ bool conv_x3_supported(int Cin, int Cout, int K, int dil) {
 // tools/cx3_bench.hip (two chunks ahead wins where a chunk's MFMAs are long enough to keep two
 // register sets without losing occupancy)
 template <int MI, int NI, int WM, int WN, int KT, int RS, int SD>
-static void cx_launch(const ConvArgs& a, hipStream_t s) {
+static int cx_launch(const ConvArgs& a, hipStream_t s) {
   constexpr int TC = 16 * MI * WM, TQ = 16 * NI * WN;
   ensure_dyn_lds((const void*)conv_x3_kernel<MI, NI, WM, WN, KT, RS, SD>, 160 * 1024);
   const int nq = (a.max_q + TQ - 1) / TQ, nco = (a.Cout + TC - 1) / TC, nz = a.B * a.nphase;
@@ -359,6 +360,7 @@ static void cx_launch(const ConvArgs& a, hipStream_t s) {
   const int per = (int)((ntile + 7) / 8);
   const size_t lds = (size_t)2 * (TQ + (KT - 1) * a.dil) * CX_XR * 2;
   conv_x3_kernel<MI, NI, WM, WN, KT, RS, SD><<<dim3(8 * per), 64 * WM * WN, lds, s>>>(a, nq, nco, nz);
+  return TQ;
 }
 
 // estimated cost of a call on one tile shape: rounds of resident workgroups x positions per tile
@@ -400,18 +402,19 @@ static long cx_cost(const ConvArgs& a) {
 }
 
 template <int MI, int NI, int WM, int WN, int SD12>
-static void cx_taps(const ConvArgs& a, hipStream_t s) {
+static int cx_taps(const ConvArgs& a, hipStream_t s) {
   switch (a.K) {
-    case 1: cx_launch<MI, NI, WM, WN, 1, 2, SD12>(a, s); break;
-    case 2: cx_launch<MI, NI, WM, WN, 2, 2 * SD12, SD12>(a, s); break;
-    case 3: cx_launch<MI, NI, WM, WN, 3, 3, 1>(a, s); break;
-    case 5: cx_launch<MI, NI, WM, WN, 5, 5, 2>(a, s); break;
-    case 7: cx_launch<MI, NI, WM, WN, 7, 7, 1>(a, s); break;
+    case 1: return cx_launch<MI, NI, WM, WN, 1, 2, SD12>(a, s);
+    case 2: return cx_launch<MI, NI, WM, WN, 2, 2 * SD12, SD12>(a, s);
+    case 3: return cx_launch<MI, NI, WM, WN, 3, 3, 1>(a, s);
+    case 5: return cx_launch<MI, NI, WM, WN, 5, 5, 2>(a, s);
+    case 7: return cx_launch<MI, NI, WM, WN, 7, 7, 1>(a, s);
     default: TTS_CHECK(false, "conv_x3: unsupported tap count");
   }
+  return 0;
 }
 
-void launch_conv_x3(const ConvArgs& a, hipStream_t s) {
+int launch_conv_x3(const ConvArgs& a, hipStream_t s) {
   TTS_CHECK(conv_x3_supported(a.Cin, a.Cout, a.K, a.dil), "conv_x3: unsupported shape");
   TTS_CHECK(a.W16 && a.oflow, "conv_x3: split weights / overflow flag missing");
   TTS_CHECK(a.nphase >= 1 && a.nphase <= 8, "conv: nphase");
@@ -421,7 +424,8 @@ void launch_conv_x3(const ConvArgs& a, hipStream_t s) {
             "conv_x3: phase-merged ConvTranspose arguments");
   TTS_CHECK(a.src[0].sc != 1 || (a.src[0].st % 4 == 0 && (reinterpret_cast<uintptr_t>(a.src[0].ptr) & 15) == 0),
             "conv_x3: time-major source rows must be 16-byte aligned");
-  if (a.max_q <= 0 || a.B <= 0) return;
+  if (a.max_q <= 0 || a.B <= 0) return 0;
+  int tq = 0;
   switch (cx_tile(a.Cout)) {
     case CX_T128: {
       // 128 x 48 or 128 x 64 tiles, whichever the round-quantised cost model prefers (ties: 64);
@@ -433,18 +437,19 @@ void launch_conv_x3(const ConvArgs& a, hipStream_t s) {
       const int force = sw::cx_ni128();
       bool narrow = force == 3;
       if (!force && a.K >= 2) narrow = cx_cost<2, 3, 4, 1, 2>(a) < cx_cost<2, 4, 4, 1, 2>(a);
-      if (narrow) cx_taps<2, 3, 4, 1, 2>(a, s);
-      else cx_taps<2, 4, 4, 1, 2>(a, s);
+      if (narrow) tq = cx_taps<2, 3, 4, 1, 2>(a, s);
+      else tq = cx_taps<2, 4, 4, 1, 2>(a, s);
       break;
     }
-    case CX_T192: cx_taps<3, 4, 4, 1, 2>(a, s); break;
-    case CX_T96: cx_taps<3, 4, 2, 2, 1>(a, s); break;
-    case CX_T64: cx_taps<2, 4, 2, 2, 1>(a, s); break;
-    case CX_T80: cx_taps<5, 2, 1, 4, 2>(a, s); break;
-    case CX_T48: cx_taps<3, 2, 1, 4, 1>(a, s); break;
+    case CX_T192: tq = cx_taps<3, 4, 4, 1, 2>(a, s); break;
+    case CX_T96: tq = cx_taps<3, 4, 2, 2, 1>(a, s); break;
+    case CX_T64: tq = cx_taps<2, 4, 2, 2, 1>(a, s); break;
+    case CX_T80: tq = cx_taps<5, 2, 1, 4, 2>(a, s); break;
+    case CX_T48: tq = cx_taps<3, 2, 1, 4, 1>(a, s); break;
     default: TTS_CHECK(false, "conv_x3: unsupported output channel count");
   }
   HIP_OK(hipGetLastError());
+  return tq;
 }
 
 // k-step ks = chunk * K + tap covers input channels 32 chunk .. 32 chunk + 31 of that tap

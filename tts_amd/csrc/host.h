@@ -147,7 +147,20 @@ struct ConvCall {
   int merged_u = 0;           // phase-merged ConvTranspose (layer from pack_conv_x3_only)
 };
 
-void run_conv(const ConvLayer& L, const ConvCall& c, hipStream_t st);
+// which kernel a run_conv launched: the split-f16 one (conv_x3.hip) or the fp32 one (conv.hip), and
+// its tile width in output positions (0: nothing was launched)
+struct ConvRan {
+  bool x3 = false;
+  int tq = 0;
+};
+ConvRan run_conv(const ConvLayer& L, const ConvCall& c, hipStream_t st);
+
+// ConvTranspose1d(k = 2u, stride u, padding u / 2) from its weight wt (Cin, Cout, 2u) and bias:
+// L = the u polyphase 2-tap convs (Wm [u][Cout][Cin][2], pad_left per phase), Lm = the phase-merged
+// split-f16 form (ConvCall::merged_u), left without weights where the merged GEMM's u * Cout rows
+// are not covered or a weight is outside the f16 range
+void pack_convT(ConvLayer& L, ConvLayer& Lm, const std::vector<float>& wt, const std::vector<float>& bias, int u,
+                int Cin, int Cout);
 
 // weight layout helpers: LSTM gate rows regrouped per 4-unit tile, column blocks of matrices with
 // equal row counts concatenated, a column range, swizzle_rows16 with the rows padded to 16, and a
