@@ -37,6 +37,9 @@
  *                                    (TTS/utils/audio.py:213-214, 241-248, 259-279)
  *   tts_stft_mag / tts_mag_to_feature <- AudioProcessor.spectrogram / melspectrogram on a batch of
  *                                    waveforms (TTS/utils/audio.py:108-124, 198-230, 259-267)
+ *   tts_pqmf_analysis             <- PQMF.analysis (TTS/vocoder/layers/pqmf.py:48-49)
+ *   tts_stft_pair_sums / tts_torch_stft_mag <- STFTLoss / TorchSTFT, evaluation only
+ *                                    (TTS/vocoder/layers/losses.py:7-52)
  *
  * Conventions: every function returns 0 on success and nonzero on failure; the message is
  * available from tts_last_error() (thread-local). Pointers prefixed d_ are device (HIP) memory
@@ -442,6 +445,39 @@ int tts_deemphasis(tts_ctx* ctx, const float* d_in, const int32_t* h_nsamples, i
 int tts_wav_finish(tts_ctx* ctx, const float* d_wav, const int32_t* h_nsamples, int B, int L_max,
                    int window_length, int hop_length, double threshold, int gap, int16_t* d_pcm, int32_t* d_ends,
                    int32_t* d_total, void* stream);
+
+/* Vocoder scoring (TTS/vocoder/layers/pqmf.py:48-49, TTS/vocoder/layers/losses.py:7-52). All three
+   only enqueue work on `stream`; rows are read for their own lengths only.
+
+   tts_pqmf_analysis <- PQMF.analysis: F.conv1d(x, H, padding = taps / 2, stride = N)
+   d_x         (B, L_max) waveforms, row b valid for h_lens[b] samples (0 <= h_lens[b] <= L_max); the
+               zero padding sits at the row's own ends
+   d_H         (N, taps + 1) analysis filters, N <= 8, taps even and <= 254
+   d_y         (B, N, Lout_max) bands; row b holds (h_lens[b] - 1) / N + 1 positions and zeros after
+               them. Plain fp32 FMA over the taps in ascending order. */
+int tts_pqmf_analysis(tts_ctx* ctx, const float* d_x, const int32_t* h_lens, int B, int L_max, int N,
+                      const float* d_H, int taps, float* d_y, int Lout_max, void* stream);
+
+/* tts_stft_pair_sums <- the sums behind STFTLoss.forward(y_hat, y) for one resolution, per row:
+     d_sums[b] = { sum |log y_M - log y_hat_M|, sum (y_M - y_hat_M)^2, sum y_M^2 }   (B, 3) float64
+   over the row's n_fft / 2 + 1 bins and 1 + (h_nsamples[b] + 2 (n_fft / 2) - n_fft) / hop_length frames,
+   M = sqrt(max(re^2 + im^2, 1e-8)) of torch.stft(x, n_fft, hop_length, win_length,
+   hann_window(win_length), center = True, pad_mode = "reflect", onesided = True).
+   d_yhat, d_y (B, L_max), row b valid for h_nsamples[b] samples, n_fft / 2 < h_nsamples[b] <= L_max
+               (a shorter row fails as in torch: "Padding size should be less than ...")
+   16 <= win_length <= n_fft <= 2048 (either parity), hop_length >= 1, B <= 64.
+   A windowed DFT as a GEMM on the fp32 MFMA, the spectra stay on chip; per-tile fp32 partial sums
+   are added per row in tile order in float64. A row's tiles depend on its own length only: its
+   sums are the same bits alone and in any batch. The first call with a new (n_fft, win_length)
+   builds and uploads its DFT basis (a blocking copy); the context keeps it. */
+int tts_stft_pair_sums(tts_ctx* ctx, const float* d_yhat, const float* d_y, const int32_t* h_nsamples, int B,
+                       int L_max, int n_fft, int win_length, int hop_length, double* d_sums, void* stream);
+
+/* tts_torch_stft_mag <- TorchSTFT.__call__: the magnitudes M above of one signal
+   d_mag       (B, n_fft / 2 + 1, frames_max), row b zero past its own frames; frames_max >= every
+               row's frame count. Other arguments and limits as tts_stft_pair_sums. */
+int tts_torch_stft_mag(tts_ctx* ctx, const float* d_wav, const int32_t* h_nsamples, int B, int L_max, int n_fft,
+                       int win_length, int hop_length, float* d_mag, int frames_max, void* stream);
 
 /* Measurement hook for bench.py: average device time (ms) of `iters` launches of one kernel of the
    last tts_taco_infer configuration, timed with hipEvents on the context's stream.

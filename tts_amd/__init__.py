@@ -11,5 +11,7 @@ from .tacotron import Tacotron  # noqa: F401
 from .tacotron2 import Tacotron2  # noqa: F401
 from .vocoder import (FullbandMelganGenerator, MelganGenerator, MultibandMelganGenerator, ParallelWaveganGenerator,  # noqa: F401
                       PQMF)
+from .vocoder_eval import copy_synthesis_scores  # noqa: F401
+from .vocoder_losses import MultiScaleSTFTLoss, MultiScaleSubbandSTFTLoss, STFTLoss, TorchSTFT  # noqa: F401
 
 __version__ = "0.1.0"

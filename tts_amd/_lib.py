@@ -117,6 +117,12 @@ SIGNATURES = [
     ("tts_deemphasis", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, _vp, _vp]),
     ("tts_wav_finish", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    ("tts_pqmf_analysis", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
+                                         ctypes.c_int, _vp, ctypes.c_int, _vp]),
+    ("tts_stft_pair_sums", ctypes.c_int, [_vp, _vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int, _vp, _vp]),
+    ("tts_torch_stft_mag", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, _vp, ctypes.c_int, _vp]),
 ]
 
 
@@ -525,6 +531,31 @@ class Engine:
         _check(self.lib.tts_wav_finish(self.h, _ptr(wav), n_p, B, L, int(window_length), int(hop_length),
                                        float(threshold), int(gap), _ptr(pcm), _ptr(ends), _ptr(total),
                                        _stream(wav.device)))
+
+    def pqmf_analysis(self, x, lens, H, y):
+        """PQMF.analysis (tts_pqmf_analysis): ``x`` (B, L_max) with ``lens[b]`` valid samples per row,
+        ``H`` (N, taps + 1) -> ``y`` (B, N, Lout_max), row b zero past (lens[b] - 1) // N + 1."""
+        B, L = x.shape
+        l_a, l_p = _i32(lens)
+        _check(self.lib.tts_pqmf_analysis(self.h, _ptr(x), l_p, B, L, H.shape[0], _ptr(H), H.shape[1] - 1, _ptr(y),
+                                          y.shape[2], _stream(x.device)))
+
+    def stft_pair_sums(self, y_hat, y, nsamples, n_fft, win_length, hop_length, sums):
+        """Per-row STFT distance sums of one resolution (tts_stft_pair_sums): ``y_hat``, ``y``
+        (B, L_max) with ``nsamples[b]`` valid samples per row -> ``sums`` (B, 3) float64:
+        sum |log y_M - log y_hat_M|, sum (y_M - y_hat_M)^2, sum y_M^2."""
+        B, L = y.shape
+        n_a, n_p = _i32(nsamples)
+        _check(self.lib.tts_stft_pair_sums(self.h, _ptr(y_hat), _ptr(y), n_p, B, L, int(n_fft), int(win_length),
+                                           int(hop_length), _ptr(sums), _stream(y.device)))
+
+    def torch_stft_mag(self, wav, nsamples, n_fft, win_length, hop_length, mag):
+        """TorchSTFT magnitudes (tts_torch_stft_mag): ``wav`` (B, L_max) -> ``mag``
+        (B, n_fft // 2 + 1, frames_max), row b zero past its own frames."""
+        B, L = wav.shape
+        n_a, n_p = _i32(nsamples)
+        _check(self.lib.tts_torch_stft_mag(self.h, _ptr(wav), n_p, B, L, int(n_fft), int(win_length),
+                                           int(hop_length), _ptr(mag), mag.shape[2], _stream(wav.device)))
 
     def conv_test(self, weight, bias, lens, src, out, max_q, device, transposed=False, K=1, dil=1, nphase=1,
                   pad_left=(0,), merged_u=0, src2=None, resid=None, resid_rows=0, aux=None, auxb=0, len_add=0,

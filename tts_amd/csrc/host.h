@@ -431,6 +431,17 @@ struct AudioWS {
   DevBuf tail;
 };
 
+// Vocoder scoring (voc_eval.hip): the DFT bases by (n_fft, win_length), kept for the context's
+// life, and the per-tile partial sums of the last tts_stft_pair_sums call
+struct VocEvalWS {
+  struct Basis {
+    DevBuf d;
+    int Kp = 0, nbt = 0;
+  };
+  std::map<std::pair<int, int>, Basis> bases;
+  DevBuf partial;
+};
+
 // one submitted fused call: what its fp32 re-run needs if the split-f16 vocoder raised the range
 // flag (the caller keeps d_post and d_wav untouched until the ticket is finished)
 struct VocTicket {
@@ -481,6 +492,7 @@ struct tts_ctx {
   ttsh::GlowModel glow;
   ttsh::GlowWS glws;
   ttsh::AudioWS aws;
+  ttsh::VocEvalWS vews;
   ttsh::HostMap t1_host;
   ttsh::T1Model t1;
   ttsh::T1WS t1ws;

@@ -186,3 +186,25 @@ void launch_stft_frames(bool fft, const float* wav, long L_max, const RowInts& n
 void launch_mag_to_feature(const float* mag, const RowInts& lens, int B, int M_max, int F, int C, const float* basis,
                            float gain, const float* scale, const float* offset, float clip_lo, float clip_hi,
                            int use_clip, float* out, hipStream_t s);
+
+// voc_eval.hip. PQMF analysis: x (B, L_max) rows of lens samples, H (N, ntap) with ntap odd, y
+// (B, N, Lout_max), row b zero past (lens[b] - 1) / N + 1 positions.
+constexpr int PQ_NMAX = 8, PQ_NTAP_MAX = 255;
+void launch_pqmf_analysis(const float* x, long L_max, const RowInts& lens, int B, const float* H, int N, int ntap,
+                          float* y, int Lout_max, hipStream_t s);
+// The windowed-DFT basis of one (n_fft, win_length) on the device, in the STFT GEMM's tile order:
+// [bin tile][Kp][cos ST_TB | sin ST_TB], d[..][k][j] = hann(k) cos / -sin(2 pi f (k + woff) / n_fft),
+// zero for k >= K = win_length and bins f >= F = n_fft / 2 + 1; Kp = K rounded up to the kernel's K chunk
+constexpr int ST_TF = 64, ST_TB = 64, ST_KCHUNK = 32;
+struct StftBasis {
+  const float* d;
+  int n_fft, K, Kp, woff, F, nbt;
+};
+// per-row sums {sum |log y_M - log yhat_M|, sum (y_M - yhat_M)^2, sum y_M^2} over the row's own frames
+// into sums (B, 3) float64; partial: B * ceil(frames_max / ST_TF) * nbt * 3 floats of scratch;
+// frames_max >= every row's frame count
+void launch_stft_pair_sums(const float* yhat, const float* y, long L_max, const RowInts& nsamp, int B,
+                           const StftBasis& W, int hop, int frames_max, float* partial, double* sums, hipStream_t s);
+// mag (B, F, frames_max) = sqrt(max(re^2 + im^2, 1e-8)), zero past a row's own frames
+void launch_stft_mag_store(const float* wav, long L_max, const RowInts& nsamp, int B, const StftBasis& W, int hop,
+                           float* mag, int frames_max, hipStream_t s);

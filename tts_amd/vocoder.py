@@ -43,8 +43,31 @@ class PQMF(Container):
             eng.pqmf_synthesis(x, G, y)
         return y
 
-    def analysis(self, x):  # training-only path in the reference (pqmf.py:48-49)
-        raise NotImplementedError("PQMF analysis is training-only and out of scope")
+    def forward(self, x):
+        return self.analysis(x)
+
+    @torch.no_grad()
+    def analysis(self, x, lengths: Optional[Sequence[int]] = None):
+        """``F.conv1d(x, H, padding=taps // 2, stride=N)`` (pqmf.py:48-49): (B, 1, L) -> (B, N,
+        (L - 1) // N + 1). Batching (new, optional): with ``lengths`` row b equals the reference call
+        on ``x[b:b+1, :, :lengths[b]]`` and is zero past ``(lengths[b] - 1) // N + 1``."""
+        x = torch.as_tensor(x)
+        eng = get_engine(x.device)
+        if x.dim() != 3 or x.shape[1] != 1:
+            raise ValueError(f"expected a (B, 1, L) waveform batch, got {tuple(x.shape)}")
+        if self.taps % 2:
+            raise NotImplementedError(f"PQMF analysis: taps={self.taps} (only an even taps is built)")
+        x = x.to(torch.float32).contiguous()
+        B, _, L = x.shape
+        lens = np.full(B, L, np.int64) if lengths is None else np.asarray(torch.as_tensor(lengths).cpu(), np.int64)
+        if lens.shape != (B,) or (lens < 0).any() or (lens > L).any():
+            raise ValueError("lengths: one value in [0, L] per row")
+        y = torch.empty(B, self.N, (L - 1) // self.N + 1, device=x.device, dtype=torch.float32)
+        H = self.H.to(x.device, torch.float32).reshape(self.N, -1).contiguous()
+        with eng.lock:
+            for b0 in range(0, B, 64):  # the library takes 64 rows per call
+                eng.pqmf_analysis(x[b0:b0 + 64, 0], lens[b0:b0 + 64], H, y[b0:b0 + 64])
+        return y
 
 
 class MelganGenerator(NativeModel):
