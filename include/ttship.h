@@ -578,6 +578,53 @@ typedef struct tts_conv_test {
 } tts_conv_test;
 int tts_test_conv(tts_ctx* ctx, tts_conv_test* d, void* stream);
 
+/* Test hook: one launch of one vocoder kernel (resblock.hip, resblock_x3.hip, resstack_x3.hip,
+   melgan_out.hip) through the production packing. The weights are packed from the host arrays with
+   the functions tts_melgan_finalize uses ([W_1x1 | W_sc] and b_1x1 + b_sc through pack_conv,
+   pack_resblock_x3 / pack_resblock_x3p, pack_convT, the output conv's transposition), the launcher
+   `kind` names is called once on the context's stream, without the switches that choose between the
+   kernels in a generator run, the stream is synchronised and what was packed is freed. A shape the
+   launcher does not cover is the library's normal error with the launcher's message; no fp32 re-run
+   is made. Only tests and tools call it.
+     kind 0: launch_resblock (fp32)            1: launch_resblock_x3 (split-f16)
+          2: launch_resstack_x3, blocks 0-2    3: the same with the fused LeakyReLU + ConvTranspose1d(u = 2)
+          4: launch_out_pqmf                   5: launch_out_conv1
+   Weights, all host: per block k (one block for kinds 0-1, three for kinds 2-3) wd (C, C, 3), bd,
+   w1 (C, C, 1), b1, ws (C, C, 1), bs and dil[k]; kind 3 ct_w (2C, C, 4), ct_b; kinds 4-5 wo (N, C, 7),
+   bo (N), N = 1 for kind 5; kind 4 G (N, taps + 1).
+   d_x / d_y: device tensors, x_strides / y_strides = {batch, channel} in elements (kinds 0-2: equal for
+   both; kind 3: d_x is the ConvTranspose's input, 2C channels at half the length; kinds 4-5: y has N rows
+   resp. one row per utterance and only its batch stride is read). Row b has (h_lens[b] + len_add) * mul
+   positions; h_lens is uploaded as the device lengths, h_bounds (or NULL: h_lens) is what the launcher
+   gets as its host lengths: per-row upper bounds, as a fused Tacotron2 -> vocoder call passes them.
+   max_q: the launcher's max_q / maxL.
+   Out: tq (output positions per tile of the kernel launched), range_flag (the split-f16 range flag
+   after the call, zeroed before it; 0 for kinds 0, 4, 5). */
+typedef struct tts_voc_test {
+  int32_t kind, C, N, taps;
+  const float* wd[3];
+  const float* bd[3];
+  const float* w1[3];
+  const float* b1[3];
+  const float* ws[3];
+  const float* bs[3];
+  int32_t dil[3];
+  const float* ct_w;
+  const float* ct_b;
+  const float* wo;
+  const float* bo;
+  const float* G;
+  const float* d_x;
+  float* d_y;
+  int64_t x_strides[2], y_strides[2];
+  const int32_t* h_lens;   /* [B], host */
+  const int32_t* h_bounds; /* [B], host, or NULL */
+  int32_t B, len_add, mul, max_q;
+  int32_t tq;          /* out */
+  uint32_t range_flag; /* out */
+} tts_voc_test;
+int tts_test_voc(tts_ctx* ctx, tts_voc_test* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

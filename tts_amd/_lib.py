@@ -100,6 +100,7 @@ SIGNATURES = [
     ("tts_set_gemm_mode", ctypes.c_int, [_vp, ctypes.c_int]),
     ("tts_test_stall_lstm", ctypes.c_int, [ctypes.c_int]),
     ("tts_test_conv", ctypes.c_int, [_vp, _vp, _vp]),
+    ("tts_test_voc", ctypes.c_int, [_vp, _vp, _vp]),
     ("tts_gemm_mode", ctypes.c_int, [_vp, _c_i_p, _c_i64_p]),
     ("tts_mel_to_linear", ctypes.c_int, [_vp, _vp, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          _vp, _vp, _vp, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_float,
@@ -145,6 +146,21 @@ class ConvTest(ctypes.Structure):
         ("q_mul", ctypes.c_int32), ("out_mul", ctypes.c_int32), ("rep_pad", ctypes.c_int32),
         ("pad_mode", ctypes.c_int32), ("epi", ctypes.c_int32),
         ("ran_x3", ctypes.c_int32), ("tq", ctypes.c_int32), ("range_flag", ctypes.c_uint32),
+    ]
+
+
+class VocTest(ctypes.Structure):
+    """``tts_voc_test`` of include/ttship.h (the descriptor of tts_test_voc)."""
+    _fields_ = [
+        ("kind", ctypes.c_int32), ("C", ctypes.c_int32), ("N", ctypes.c_int32), ("taps", ctypes.c_int32),
+        ("wd", _vp * 3), ("bd", _vp * 3), ("w1", _vp * 3), ("b1", _vp * 3), ("ws", _vp * 3), ("bs", _vp * 3),
+        ("dil", ctypes.c_int32 * 3),
+        ("ct_w", _vp), ("ct_b", _vp), ("wo", _vp), ("bo", _vp), ("G", _vp),
+        ("d_x", _vp), ("d_y", _vp),
+        ("x_strides", ctypes.c_int64 * 2), ("y_strides", ctypes.c_int64 * 2),
+        ("h_lens", _vp), ("h_bounds", _vp),
+        ("B", ctypes.c_int32), ("len_add", ctypes.c_int32), ("mul", ctypes.c_int32), ("max_q", ctypes.c_int32),
+        ("tq", ctypes.c_int32), ("range_flag", ctypes.c_uint32),
     ]
 
 
@@ -598,6 +614,55 @@ class Engine:
         with self.lock:
             _check(self.lib.tts_test_conv(self.h, ctypes.c_void_p(ctypes.addressof(d)), _stream(device)))
         return bool(d.ran_x3), int(d.tq), int(d.range_flag)
+
+    def voc_test(self, kind, C, lens, x, y, max_q, device, blocks=(), ct=None, out=None, G=None, bounds=None,
+                 len_add=0, mul=1):
+        """One vocoder kernel launch through the loaders' packing (tts_test_voc; tests and tools).
+        ``kind``: 0 resblock fp32, 1 resblock_x3, 2 resstack_x3, 3 resstack_x3 with the fused
+        ConvTranspose, 4 output conv + PQMF, 5 full-band output conv. ``blocks``: per block
+        (wd, bd, w1, b1, ws, bs, dil) as numpy; ``ct``: (ct_w, ct_b); ``out``: (wo, bo); ``G``: the PQMF
+        synthesis filter (N, taps + 1); ``x`` / ``y``: (device address, (batch stride, channel stride));
+        ``bounds``: the launcher's host lengths when they are upper bounds of ``lens``. Returns
+        (tq, range_flag)."""
+        keep = []
+
+        def f32(a):
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            keep.append(a)
+            return a.ctypes.data
+
+        d = VocTest()
+        d.kind, d.C = int(kind), int(C)
+        for k, blk in enumerate(blocks):
+            wd, bd, w1, b1, ws, bs, dil = blk
+            assert np.shape(wd) == (C, C, 3) and np.size(w1) == C * C and np.size(ws) == C * C
+            assert np.size(bd) == C and np.size(b1) == C and np.size(bs) == C
+            d.wd[k], d.bd[k], d.w1[k], d.b1[k], d.ws[k], d.bs[k] = f32(wd), f32(bd), f32(w1), f32(b1), f32(ws), f32(bs)
+            d.dil[k] = int(dil)
+        if ct is not None:
+            assert np.shape(ct[0]) == (2 * C, C, 4) and np.size(ct[1]) == C
+            d.ct_w, d.ct_b = f32(ct[0]), f32(ct[1])
+        if out is not None:
+            d.N = int(np.shape(out[0])[0])
+            assert np.shape(out[0]) == (d.N, C, 7) and np.size(out[1]) == d.N
+            d.wo, d.bo = f32(out[0]), f32(out[1])
+        if G is not None:
+            assert np.ndim(G) == 2 and np.shape(G)[0] == d.N
+            d.taps = int(np.shape(G)[1]) - 1
+            d.G = f32(G)
+        lens_a = np.ascontiguousarray(lens, dtype=np.int32)
+        d.h_lens = lens_a.ctypes.data
+        if bounds is not None:
+            bounds_a = np.ascontiguousarray(bounds, dtype=np.int32)
+            assert bounds_a.shape == lens_a.shape
+            d.h_bounds = bounds_a.ctypes.data
+        d.d_x, d.d_y = x[0], y[0]
+        for j in range(2):
+            d.x_strides[j], d.y_strides[j] = x[1][j], y[1][j]
+        d.B, d.len_add, d.mul, d.max_q = len(lens_a), int(len_add), int(mul), int(max_q)
+        with self.lock:
+            _check(self.lib.tts_test_voc(self.h, ctypes.c_void_p(ctypes.addressof(d)), _stream(device)))
+        return int(d.tq), int(d.range_flag)
 
     def decoder_stats(self):
         """(path, [(ms, steps) per persistent launch]) of the last Tacotron2 decode."""

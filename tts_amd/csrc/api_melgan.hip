@@ -9,6 +9,59 @@
 
 using namespace ttsh;
 
+namespace {
+
+// One ResidualStack block's device weights from its three convs (shared by melgan_finalize and
+// tts_test_voc): the dilated conv, [W_1x1 | W_sc] with b_1x1 + b_sc as one 1x1 conv over [lrelu(h); x],
+// and where the channel count is covered the split-f16 fragments of both (resblock_x3.hip; phase 1
+// also in resstack_x3's packed order when C % 32 == 16)
+struct ResBlockPack {
+  ConvLayer &dconv, &fused;
+  DevBuf &wd16, &wf16, &wd16p;
+};
+void pack_res_block(const ResBlockPack& P, const std::vector<float>& wd, const std::vector<float>& bd,
+                    const std::vector<float>& w1, const std::vector<float>& b1, const std::vector<float>& ws,
+                    const std::vector<float>& bs, int C, int dil) {
+  int pld[8] = {dil}, pl0[8] = {0};
+  pack_conv(P.dconv, wd, bd, C, C, 3, dil, 1, pld);
+  std::vector<float> Wf((size_t)C * 2 * C), bf(C);
+  for (int co = 0; co < C; ++co) {
+    std::memcpy(&Wf[(size_t)co * 2 * C], &w1[(size_t)co * C], C * 4);
+    std::memcpy(&Wf[(size_t)co * 2 * C + C], &ws[(size_t)co * C], C * 4);
+    bf[co] = b1[co] + bs[co];
+  }
+  pack_conv(P.fused, Wf, bf, 2 * C, C, 1, 1, 1, pl0);
+  if (resblock_x3_supported(C)) {
+    std::vector<uint16_t> wd16, wf16;
+    pack_resblock_x3(wd, Wf, C, wd16, wf16);
+    P.wd16.upload(wd16);
+    P.wf16.upload(wf16);
+    if (C % 32 == 16) {
+      pack_resblock_x3p(wd, C, wd16);
+      P.wd16p.upload(wd16);
+    }
+  }
+}
+
+// The output conv's weight (out_ch, C, 7) for the VALU output kernels (melgan_out.hip): [c][k][o]
+// for the fused output + PQMF kernel (out_ch = 4), [c][k] as it is for the full-band one (out_ch = 1)
+void pack_out_conv(DevBuf& out_w, DevBuf& out_b, const std::vector<float>& w, const std::vector<float>& bo, int C,
+                   int out_ch) {
+  if (out_ch == 4) {
+    std::vector<float> wo((size_t)C * 7 * 4);
+    for (int o = 0; o < 4; ++o)
+      for (int ci = 0; ci < C; ++ci)
+        for (int k = 0; k < 7; ++k) wo[((size_t)ci * 7 + k) * 4 + o] = w[((size_t)o * C + ci) * 7 + k];
+    out_w.upload(wo);
+    out_b.upload(bo);
+  } else if (out_ch == 1) {
+    out_w.upload(w);
+    out_b.upload(bo);
+  }
+}
+
+}  // namespace
+
 static void melgan_finalize(tts_ctx* c, int in_ch, int out_ch, int base, const int32_t* ups, int n_up, int nres,
                      int use_pqmf) {
   auto& G = c->mg;
@@ -35,7 +88,7 @@ static void melgan_finalize(tts_ctx* c, int in_ch, int out_ch, int base, const i
   G.rb_wf16.resize((size_t)n_up * nres);
   G.rb_wd16p.clear();
   G.rb_wd16p.resize((size_t)n_up * nres);
-  int pl3[8] = {3}, pl0[8] = {0};
+  int pl3[8] = {3};
   {
     auto w = wn_weight(m, "layers.1", {base, in_ch, 7});
     pack_conv(G.conv_in, w, need(m, "layers.1.bias", {base}).d, in_ch, base, 7, 1, 1, pl3);
@@ -50,36 +103,14 @@ static void melgan_finalize(tts_ctx* c, int in_ch, int out_ch, int base, const i
     pack_convT(G.convT[i], G.convTm[i], wt, need(m, nm + ".bias", {cout}).d, u, cin, cout);
     C = cout;
     for (int bk = 0; bk < nres; ++bk) {
-      const int d = 1;
       int dil = 1;
       for (int q = 0; q < bk; ++q) dil *= 3;
-      (void)d;
       const std::string bn = "layers." + std::to_string(idx + 2) + ".blocks." + std::to_string(bk);
-      auto wd = wn_weight(m, bn + ".2", {C, C, 3});
-      int pld[8] = {dil};
-      pack_conv(G.dconv[(size_t)i * nres + bk], wd, need(m, bn + ".2.bias", {C}).d, C, C, 3, dil, 1, pld);
-      auto w1 = wn_weight(m, bn + ".4", {C, C, 1});
       const std::string sn = "layers." + std::to_string(idx + 2) + ".shortcuts." + std::to_string(bk);
-      auto ws = wn_weight(m, sn, {C, C, 1});
-      std::vector<float> Wf((size_t)C * 2 * C), bf(C);
-      const auto& b1 = need(m, bn + ".4.bias", {C}).d;
-      const auto& bs = need(m, sn + ".bias", {C}).d;
-      for (int co = 0; co < C; ++co) {
-        std::memcpy(&Wf[(size_t)co * 2 * C], &w1[(size_t)co * C], C * 4);
-        std::memcpy(&Wf[(size_t)co * 2 * C + C], &ws[(size_t)co * C], C * 4);
-        bf[co] = b1[co] + bs[co];
-      }
-      pack_conv(G.fused[(size_t)i * nres + bk], Wf, bf, 2 * C, C, 1, 1, 1, pl0);
-      if (resblock_x3_supported(C)) {
-        std::vector<uint16_t> wd16, wf16;
-        pack_resblock_x3(wd, Wf, C, wd16, wf16);
-        G.rb_wd16[(size_t)i * nres + bk].upload(wd16);
-        G.rb_wf16[(size_t)i * nres + bk].upload(wf16);
-        if (C % 32 == 16) {
-          pack_resblock_x3p(wd, C, wd16);
-          G.rb_wd16p[(size_t)i * nres + bk].upload(wd16);
-        }
-      }
+      const size_t j = (size_t)i * nres + bk;
+      pack_res_block({G.dconv[j], G.fused[j], G.rb_wd16[j], G.rb_wf16[j], G.rb_wd16p[j]}, wn_weight(m, bn + ".2", {C, C, 3}),
+                     need(m, bn + ".2.bias", {C}).d, wn_weight(m, bn + ".4", {C, C, 1}), need(m, bn + ".4.bias", {C}).d,
+                     wn_weight(m, sn, {C, C, 1}), need(m, sn + ".bias", {C}).d, C, dil);
     }
     idx += 3;
   }
@@ -89,17 +120,7 @@ static void melgan_finalize(tts_ctx* c, int in_ch, int out_ch, int base, const i
     const auto& bo = need(m, nm + ".bias", {out_ch}).d;
     pack_conv(G.conv_out, w, bo, C, out_ch, 7, 1, 1, pl3);
     G.C_last = C;
-    if (out_ch == 4) {
-      std::vector<float> wo((size_t)C * 7 * 4);
-      for (int o = 0; o < 4; ++o)
-        for (int ci = 0; ci < C; ++ci)
-          for (int k = 0; k < 7; ++k) wo[((size_t)ci * 7 + k) * 4 + o] = w[((size_t)o * C + ci) * 7 + k];
-      G.out_w.upload(wo);
-      G.out_b.upload(bo);
-    } else if (out_ch == 1) {  // full-band: [c][k] for launch_out_conv1
-      G.out_w.upload(w);
-      G.out_b.upload(bo);
-    }
+    pack_out_conv(G.out_w, G.out_b, w, bo, C, out_ch);
   }
   if (use_pqmf) {
     const auto& g = need(m, "pqmf_layer.G", {}).d;
@@ -426,6 +447,118 @@ int tts_melgan_infer_strided(tts_ctx* c, const float* d_mel, int64_t stride_b, i
                              const int32_t* h_lens, int B, int M_max, int pad, float* d_wav, void* stream) {
   const int64_t st[3] = {stride_b, stride_c, stride_t};
   return melgan_infer_impl(c, d_mel, st, h_lens, B, M_max, pad, d_wav, stream);
+}
+
+int tts_test_voc(tts_ctx* c, tts_voc_test* d, void* stream) {
+  return guarded_ctx(c, [&] {
+    TTS_CHECK(d && d->d_x && d->d_y && d->h_lens, "test_voc: null argument");
+    TTS_CHECK(d->kind >= 0 && d->kind <= 5, "test_voc: kind must be in [0, 5]");
+    TTS_CHECK(d->C >= 16 && d->C % 16 == 0 && d->C <= 1024 && d->B >= 1 && d->B <= 4096 && d->max_q >= 0 && d->mul >= 1,
+              "test_voc: sizes");
+    const int kind = d->kind, C = d->C, B = d->B;
+    const int nblk = kind <= 1 ? 1 : (kind <= 3 ? 3 : 0);
+    for (int k = 0; k < nblk; ++k)
+      TTS_CHECK(d->wd[k] && d->bd[k] && d->w1[k] && d->b1[k] && d->ws[k] && d->bs[k], "test_voc: null block weights");
+    TTS_CHECK(kind != 3 || (d->ct_w && d->ct_b), "test_voc: null ConvTranspose weights");
+    TTS_CHECK(kind < 4 || (d->wo && d->bo && (kind == 5 || d->G)), "test_voc: null output weights");
+    TTS_CHECK(kind != 4 || (d->N >= 1 && d->N <= 8 && d->taps >= 0), "test_voc: bands / taps");
+    for (int i = 0; i < 2; ++i)
+      TTS_CHECK(d->x_strides[i] >= 0 && d->y_strides[i] >= 0 && d->x_strides[1] < (1L << 31) && d->y_strides[1] < (1L << 31),
+                "test_voc: strides");
+    TTS_CHECK(kind >= 3 || (d->x_strides[0] == d->y_strides[0] && d->x_strides[1] == d->y_strides[1]),
+              "test_voc: the block and stack kernels take one pair of strides for x and y");
+    d->tq = 0;
+    d->range_flag = 0;
+    DeviceGuard g(c->device);
+    enter(c, stream);
+    const int32_t* bounds = d->h_bounds ? d->h_bounds : d->h_lens;
+    // everything packed here is freed when this scope ends: wait for the launch first, also on an error
+    ConvLayer dconv[3], fused[3], ctL, ctM;
+    DevBuf wd16[3], wf16[3], wd16p[3], out_w, out_b, Gd, lens;
+    struct Sync {
+      hipStream_t s;
+      ~Sync() { (void)hipStreamSynchronize(s); }
+    } sync{c->s};
+    auto vec = [](const float* p, size_t n) { return std::vector<float>(p, p + n); };
+    for (int k = 0; k < nblk; ++k)
+      pack_res_block({dconv[k], fused[k], wd16[k], wf16[k], wd16p[k]}, vec(d->wd[k], (size_t)C * C * 3), vec(d->bd[k], C),
+                     vec(d->w1[k], (size_t)C * C), vec(d->b1[k], C), vec(d->ws[k], (size_t)C * C), vec(d->bs[k], C), C,
+                     d->dil[k]);
+    c->x3flag.ensure(4);
+    unsigned* flag = reinterpret_cast<unsigned*>(c->x3flag.p);
+    HIP_OK(hipMemsetAsync(flag, 0, 4, c->s));
+    const int* dl = put_rows(lens, d->h_lens, B, c->s);
+    if (kind <= 1) {
+      ResArgs ra{};
+      ra.x = d->d_x;
+      ra.y = d->d_y;
+      ra.sb = (long)d->y_strides[0];
+      ra.Ls = (int)d->y_strides[1];
+      ra.lens = dl;
+      ra.len_add = d->len_add;
+      ra.mul = d->mul;
+      ra.dil = dconv[0].dil;
+      ra.Wd = dconv[0].W.f();
+      ra.bd = dconv[0].bias.f();
+      ra.Wf = fused[0].W.f();
+      ra.bf = fused[0].bias.f();
+      ra.max_q = d->max_q;
+      ra.B = B;
+      if (kind == 1) {
+        ra.Wd16 = wd16[0].p;
+        ra.Wf16 = wf16[0].p;
+        ra.oflow = flag;
+        d->tq = launch_resblock_x3(ra, bounds, C, c->s);
+      } else {
+        d->tq = launch_resblock(ra, C, c->s);
+      }
+    } else if (kind <= 3) {
+      StackArgs sa{};
+      sa.B = B;
+      sa.x = kind == 2 ? d->d_x : nullptr;
+      sa.y = d->d_y;
+      sa.sb = (long)d->y_strides[0];
+      sa.Ls = (int)d->y_strides[1];
+      sa.lens = dl;
+      sa.len_add = d->len_add;
+      sa.mul = d->mul;
+      for (int k = 0; k < 3; ++k) {
+        sa.dil[k] = dconv[k].dil;
+        sa.wd16[k] = C % 32 == 16 ? wd16p[k].p : wd16[k].p;
+        sa.wf16[k] = wf16[k].p;
+        sa.bd[k] = dconv[k].bias.f();
+        sa.bf[k] = fused[k].bias.f();
+      }
+      sa.oflow = flag;
+      if (kind == 3) {
+        pack_convT(ctL, ctM, vec(d->ct_w, (size_t)2 * C * C * 4), vec(d->ct_b, C), 2, 2 * C, C);
+        TTS_CHECK(ctM.W16.p, "test_voc: the merged ConvTranspose has no split-f16 weights");
+        sa.xin = d->d_x;
+        sa.sb_in = (long)d->x_strides[0];
+        sa.Ls_in = (int)d->x_strides[1];
+        sa.ct16 = ctM.W16.p;
+        sa.ct_bias = ctM.bias.f();
+      }
+      d->tq = launch_resstack_x3(sa, bounds, C, c->s);
+    } else if (kind == 4) {
+      pack_out_conv(out_w, out_b, vec(d->wo, (size_t)d->N * C * 7), vec(d->bo, d->N), C, d->N);
+      TTS_CHECK(out_w.p, "fused output/PQMF shape not covered");
+      Gd.upload(vec(d->G, (size_t)d->N * (d->taps + 1)));
+      int tq = 0;
+      TTS_CHECK(launch_out_pqmf(d->d_x, (long)d->x_strides[0], (long)d->x_strides[1], C, out_w.f(), out_b.f(), Gd.f(), d->N,
+                                d->taps, dl, d->len_add, d->mul, d->max_q, B, d->d_y, (long)d->y_strides[0], c->s, &tq),
+                "fused output/PQMF shape not covered");
+      d->tq = tq;
+    } else {
+      pack_out_conv(out_w, out_b, vec(d->wo, (size_t)C * 7), vec(d->bo, 1), C, 1);
+      d->tq = launch_out_conv1(d->d_x, (long)d->x_strides[0], (long)d->x_strides[1], C, out_w.f(), out_b.f(), dl, d->len_add,
+                               d->mul, d->max_q, B, d->d_y, (long)d->y_strides[0], c->s);
+    }
+    HIP_OK(hipMemcpyAsync(&c->pinned[PIN_FLAG], flag, 4, hipMemcpyDeviceToHost, c->s));
+    HIP_OK(hipStreamSynchronize(c->s));
+    d->range_flag = (uint32_t)c->pinned[PIN_FLAG];
+    leave(c, stream);
+  });
 }
 
 int tts_pqmf_synthesis(tts_ctx* c, const float* d_x, int B, int N, int L, const float* d_G, int taps, float* d_y,

@@ -219,12 +219,14 @@ struct ResArgs {
   const void* Wf16 = nullptr;
   unsigned* oflow = nullptr;
 };
-void launch_resblock(const ResArgs& a, int C, hipStream_t s);
+// the block and stack launchers return the tile width TQ (output positions per workgroup tile) of
+// the kernel they chose (0: nothing to launch)
+int launch_resblock(const ResArgs& a, int C, hipStream_t s);
 bool resblock_x3_supported(int C);
 // persistent: one workgroup per CU loops over the (utterance, position) tiles; h_lens = the
 // host copy of lens, or per-row upper bounds of the device lens (grid size; the kernel counts
 // the tiles from the device lens)
-void launch_resblock_x3(const ResArgs& a, const int* h_lens, int C, hipStream_t s);
+int launch_resblock_x3(const ResArgs& a, const int* h_lens, int C, hipStream_t s);
 void pack_resblock_x3(const std::vector<float>& wd, const std::vector<float>& wf, int C,
                       std::vector<uint16_t>& wd16, std::vector<uint16_t>& wf16);
 // phase-1 weights in resstack_x3's packed order for C % 32 == 16 (C = 48: 5 k-steps, not 6)
@@ -258,16 +260,18 @@ struct StackArgs {
 };
 bool resstack_x3_supported(int C, const int* dil, int n);
 bool resstack_x3_fits(const StackArgs& a, const int* h_lens);
-void launch_resstack_x3(const StackArgs& a, const int* h_lens, int C, hipStream_t s);
+int launch_resstack_x3(const StackArgs& a, const int* h_lens, int C, hipStream_t s);
 
 // fused MB-MelGAN output conv (C -> 4, k7, LReLU + reflect pad 3 + tanh) and PQMF synthesis
 // (melgan_out.hip); returns false when the shape is not covered (N != 4, 63 taps, C not 32/48).
-// launch_out_pqmf writes every row's band positions [0, maxL): zeros past its own length
-void launch_out_conv1(const float* x, long xb, long xc, int C, const float* W, const float* bo, const int* lens,
+// launch_out_pqmf writes every row's band positions [0, maxL): zeros past its own length.
+// launch_out_conv1 returns the output positions per workgroup (0: nothing to launch); launch_out_pqmf
+// writes the band positions per workgroup to *tq when given
+int launch_out_conv1(const float* x, long xb, long xc, int C, const float* W, const float* bo, const int* lens,
                       int len_add, int L_mul, int maxL, int B, float* y, long yb, hipStream_t s);
 bool launch_out_pqmf(const float* x, long xb, long xc, int C, const float* Wo, const float* bo, const float* G,
                      int N, int taps, const int* lens, int len_add, int L_mul, int maxL, int B, float* y, long yb,
-                     hipStream_t s);
+                     hipStream_t s, int* tq = nullptr);
 // test hook of the persistent BiLSTM (tts_test_stall_lstm): recurrence to stall, -1 = off
 extern std::atomic<int> g_test_stall_lstm;
 

@@ -165,7 +165,8 @@ __global__ __launch_bounds__(256) void out_pqmf_kernel(const float* __restrict__
 
 bool launch_out_pqmf(const float* x, long xb, long xc, int C, const float* Wo, const float* bo, const float* G,
                      int N, int taps, const int* lens, int len_add, int L_mul, int maxL, int B, float* y, long yb,
-                     hipStream_t s) {
+                     hipStream_t s, int* tq) {
+  if (tq) *tq = OP_TB;
   if (N != OP_N || taps + 1 != OP_TAPS) return false;
   if (maxL <= 0 || B <= 0) return true;
   if (yb % 4 != 0 || (reinterpret_cast<uintptr_t>(y) & 15) != 0) return false;  // float4 output stores
@@ -255,13 +256,14 @@ __global__ __launch_bounds__(256) void out_conv1_kernel(const float* __restrict_
   }
 }
 
-void launch_out_conv1(const float* x, long xb, long xc, int C, const float* W, const float* bo, const int* lens,
+int launch_out_conv1(const float* x, long xb, long xc, int C, const float* W, const float* bo, const int* lens,
                       int len_add, int L_mul, int maxL, int B, float* y, long yb, hipStream_t s) {
-  if (maxL <= 0 || B <= 0) return;
+  if (maxL <= 0 || B <= 0) return 0;
   const int vec = (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0 &&
                   xb % 4 == 0 && xc % 4 == 0 && yb % 4 == 0;
   const int per = 256 * OC1_P;
   out_conv1_kernel<<<dim3((maxL + per - 1) / per, B), 256, 0, s>>>(x, xb, xc, C, W, bo, lens, len_add, L_mul, y, yb,
                                                                     vec);
   HIP_OK(hipGetLastError());
+  return per;
 }

@@ -189,26 +189,29 @@ __global__ __launch_bounds__(64 * WM * WN) void resblock_kernel(ResArgs a) {
 }
 
 template <int C, int TQ, int WM, int WN>
-static void launch_rb(const ResArgs& a, hipStream_t s) {
+static int launch_rb(const ResArgs& a, hipStream_t s) {
   const int ROW = TQ + 2 * a.dil + 1;
   const size_t lds = ((size_t)2 * ((16 * ROW + 3) & ~3) + (size_t)2 * C * TQ) * 4;
   dim3 grid((a.max_q + TQ - 1) / TQ, a.B);
   resblock_kernel<C, TQ, WM, WN><<<grid, 64 * WM * WN, lds, s>>>(a);
+  return TQ;
 }
 
-void launch_resblock(const ResArgs& a, int C, hipStream_t s) {
+int launch_resblock(const ResArgs& a, int C, hipStream_t s) {
   TTS_CHECK(a.dil >= 1 && a.dil <= RB_DMAX, "resblock: dilation must be in [1, 27] (num_res_blocks <= 4)");
-  if (a.max_q <= 0 || a.B <= 0) return;
+  if (a.max_q <= 0 || a.B <= 0) return 0;
+  int tq = 0;
   // tiles from tools/voc_bench.hip (C2 shapes)
   switch (C) {
-    case 192: launch_rb<192, 32, 4, 1>(a, s); break;
-    case 96: launch_rb<96, 64, 2, 2>(a, s); break;
-    case 48: launch_rb<48, 128, 1, 8>(a, s); break;
-    case 256: launch_rb<256, 32, 4, 1>(a, s); break;
-    case 128: launch_rb<128, 64, 2, 2>(a, s); break;
-    case 64: launch_rb<64, 128, 1, 8>(a, s); break;
-    case 32: launch_rb<32, 64, 1, 4>(a, s); break;
+    case 192: tq = launch_rb<192, 32, 4, 1>(a, s); break;
+    case 96: tq = launch_rb<96, 64, 2, 2>(a, s); break;
+    case 48: tq = launch_rb<48, 128, 1, 8>(a, s); break;
+    case 256: tq = launch_rb<256, 32, 4, 1>(a, s); break;
+    case 128: tq = launch_rb<128, 64, 2, 2>(a, s); break;
+    case 64: tq = launch_rb<64, 128, 1, 8>(a, s); break;
+    case 32: tq = launch_rb<32, 64, 1, 4>(a, s); break;
     default: TTS_CHECK(false, "resblock: unsupported channel count");
   }
   HIP_OK(hipGetLastError());
+  return tq;
 }

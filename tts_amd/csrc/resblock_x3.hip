@@ -94,7 +94,7 @@ __global__ __launch_bounds__(64 * WM * WN) void resblock_x3_kernel(ResArgs a, in
   const int kgsw = kg ^ lsw;
   const int kgx[3] = {kgsw, kg ^ lds_rsw((lane & 15) + d), kg ^ lds_rsw((lane & 15) + 2 * d)};
   const int mt0 = wm * MI;
-  bool bad = false;   // staged inputs: ordered compare (catches NaN)
+  bool bad = false;   // staged inputs: IEEE maximum of |v|, then an ordered compare (a NaN sets it)
   float vmax = 0.f;   // h values: running max of |h| (split16.h absmax4)
 
   // tile index -> (utterance, first position): x3_tile.h
@@ -152,7 +152,8 @@ __global__ __launch_bounds__(64 * WM * WN) void resblock_x3_kernel(ResArgs a, in
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
           v[c] = real ? sr[j][c] : 0.f;
-          mx = fmaxf(mx, __builtin_fabsf(v[c]));
+          // IEEE-754 maximum (v_maximum3_f32): keeps a NaN, which fmaxf would drop
+          mx = __builtin_elementwise_maximum(mx, __builtin_fabsf(v[c]));
         }
         bad |= !(mx < F16_RANGE);  // |lrelu(v)| <= |v|: one check covers both splits
         float lv[8];
@@ -359,17 +360,18 @@ __global__ __launch_bounds__(64 * WM * WN) void resblock_x3_kernel(ResArgs a, in
 // dynamic LDS leaves 1 KiB of the CU's 160 KiB for the kernel's static tile tables
 constexpr int RB_DYN_LDS = 159 * 1024;
 template <int C, int TQ, int WM, int WN, int R, int CPB = 1>
-static void launch_rbx3(const ResArgs& a, const int* h_lens, hipStream_t s) {
+static int launch_rbx3(const ResArgs& a, const int* h_lens, hipStream_t s) {
   const int ROWS = TQ + 2 * a.dil;
   const size_t lds = ((size_t)2 * ROWS * (64 * CPB + 16) + (size_t)TQ * (4 * C + 16)) * 2;
   ensure_dyn_lds((const void*)resblock_x3_kernel<C, TQ, WM, WN, R, CPB>, RB_DYN_LDS);
   const int ncu = device_cu_count();
   TTS_CHECK(lds <= RB_DYN_LDS, "resblock_x3: LDS tile too large");
   const long ntiles = x3_tile_count(h_lens, a.B, a.len_add, a.mul, TQ, "resblock_x3");
-  if (ntiles == 0) return;
+  if (ntiles == 0) return 0;
   const int grid = (int)std::min<long>(ntiles, ncu);
   const bool vec = a.Ls % 4 == 0 && a.sb % 4 == 0 && (reinterpret_cast<uintptr_t>(a.y) & 15) == 0;
   resblock_x3_kernel<C, TQ, WM, WN, R, CPB><<<grid, 64 * WM * WN, lds, s>>>(a, (int)ntiles, vec);
+  return TQ;
 }
 
 bool resblock_x3_supported(int C) { return C == 256 || C == 192 || C == 128 || C == 96 || C == 64 || C == 48 || C == 32; }
@@ -410,22 +412,24 @@ void pack_resblock_x3p(const std::vector<float>& wd, int C, std::vector<uint16_t
   });
 }
 
-void launch_resblock_x3(const ResArgs& a, const int* h_lens, int C, hipStream_t s) {
+int launch_resblock_x3(const ResArgs& a, const int* h_lens, int C, hipStream_t s) {
   TTS_CHECK(a.dil >= 1 && a.dil <= X3_DMAX, "resblock: dilation must be in [1, 27] (num_res_blocks <= 4)");
   TTS_CHECK(a.Wd16 && a.Wf16 && a.oflow, "resblock_x3: split weights / overflow flag missing");
   TTS_CHECK(a.B <= 64, "resblock_x3: at most 64 utterances per call");
-  if (a.max_q <= 0 || a.B <= 0) return;
+  if (a.max_q <= 0 || a.B <= 0) return 0;
+  int tq = 0;
   switch (C) {
     // tiles from tools/rbx3_bench.hip (C2 shapes): 12 waves, one m-tile (or two) per wave
-    case 192: launch_rbx3<192, 64, 12, 1, 3>(a, h_lens, s); break;
-    case 96: launch_rbx3<96, 128, 6, 2, 3>(a, h_lens, s); break;  // round 3: 4 blocks 926 -> 879 us
-    case 48: launch_rbx3<48, 192, 3, 4, 3>(a, h_lens, s); break;
+    case 192: tq = launch_rbx3<192, 64, 12, 1, 3>(a, h_lens, s); break;
+    case 96: tq = launch_rbx3<96, 128, 6, 2, 3>(a, h_lens, s); break;  // round 3: 4 blocks 926 -> 879 us
+    case 48: tq = launch_rbx3<48, 192, 3, 4, 3>(a, h_lens, s); break;
     // full-band MelGAN stages (base 512): tiles sized to the 159 KB LDS budget, 8 waves
-    case 256: launch_rbx3<256, 32, 8, 1, 4>(a, h_lens, s); break;
-    case 128: launch_rbx3<128, 64, 8, 1, 4>(a, h_lens, s); break;
-    case 64: launch_rbx3<64, 128, 4, 2, 2>(a, h_lens, s); break;
-    case 32: launch_rbx3<32, 192, 2, 4, 1>(a, h_lens, s); break;
+    case 256: tq = launch_rbx3<256, 32, 8, 1, 4>(a, h_lens, s); break;
+    case 128: tq = launch_rbx3<128, 64, 8, 1, 4>(a, h_lens, s); break;
+    case 64: tq = launch_rbx3<64, 128, 4, 2, 2>(a, h_lens, s); break;
+    case 32: tq = launch_rbx3<32, 192, 2, 4, 1>(a, h_lens, s); break;
     default: TTS_CHECK(false, "resblock_x3: unsupported channel count");
   }
   HIP_OK(hipGetLastError());
+  return tq;
 }

@@ -104,7 +104,7 @@ __global__ __launch_bounds__(64 * (C / 16) * WN) void resstack_x3_kernel(StackAr
   // rows nt * 16 + (lane & 15) (epilogues, phase 2): the swizzled channel / k offsets
   const int lsw = lds_rsw(lane & 15);
   const int cosw = co ^ lsw, kgsw = kg ^ lsw;
-  bool bad = false;   // staged inputs: ordered compare (catches NaN)
+  bool bad = false;   // staged inputs: IEEE maximum of |v|, then an ordered compare (a NaN sets it)
   float vmax = 0.f;   // produced values: running max of |v| (split16.h absmax4)
   int t = blockIdx.x;
 
@@ -177,7 +177,7 @@ __global__ __launch_bounds__(64 * (C / 16) * WN) void resstack_x3_kernel(StackAr
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
         const float v = in ? st[j][c] : 0.f;
-        mx = fmaxf(mx, __builtin_fabsf(v));
+        mx = __builtin_elementwise_maximum(mx, __builtin_fabsf(v));  // IEEE maximum: keeps a NaN (fmaxf drops it)
         lv[c] = lrelu_s(v);
       }
       bad |= !(mx < F16_RANGE);
@@ -209,7 +209,7 @@ __global__ __launch_bounds__(64 * (C / 16) * WN) void resstack_x3_kernel(StackAr
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
         v[c] = in ? st[j][c] : 0.f;
-        mx = fmaxf(mx, __builtin_fabsf(v[c]));
+        mx = __builtin_elementwise_maximum(mx, __builtin_fabsf(v[c]));  // IEEE maximum: keeps a NaN (fmaxf drops it)
         lv[c] = lrelu_s(v[c]);
       }
       bad |= !(mx < F16_RANGE);
@@ -516,16 +516,17 @@ __global__ __launch_bounds__(64 * (C / 16) * WN) void resstack_x3_kernel(StackAr
 }
 
 template <int C, int TQ, int WN, int NI, int CTU = 0>
-static void launch_rsx3(const StackArgs& a, const int* h_lens, hipStream_t s) {
+static int launch_rsx3(const StackArgs& a, const int* h_lens, hipStream_t s) {
   constexpr int ROWS = TQ + 2 * ST_OFF;
   constexpr size_t lds = (size_t)ROWS * ((2 * C + 16) + (4 * C + 16)) * 2;
   static_assert(lds + 3 * 2 * C * 4 + 65 * 4 + 64 * 4 <= 160 * 1024, "LDS");
   ensure_dyn_lds((const void*)resstack_x3_kernel<C, TQ, WN, NI, CTU>, (int)lds);
   const int ncu = device_cu_count();
   const long ntiles = x3_tile_count(h_lens, a.B, a.len_add, a.mul, TQ, "resstack_x3");
-  if (ntiles == 0) return;
+  if (ntiles == 0) return 0;
   const int grid = (int)std::min<long>(ntiles, ncu);
   resstack_x3_kernel<C, TQ, WN, NI, CTU><<<grid, 64 * (C / 16) * WN, lds, s>>>(a, (int)ntiles);
+  return TQ;
 }
 
 bool resstack_x3_supported(int C, const int* dil, int n) {
@@ -547,7 +548,7 @@ bool resstack_x3_fits(const StackArgs& a, const int* h_lens) {
   return true;
 }
 
-void launch_resstack_x3(const StackArgs& a0, const int* h_lens, int C, hipStream_t s) {
+int launch_resstack_x3(const StackArgs& a0, const int* h_lens, int C, hipStream_t s) {
   TTS_CHECK(resstack_x3_supported(C, a0.dil, 3), "resstack_x3: shape not covered");
   TTS_CHECK(a0.oflow, "resstack_x3: overflow flag missing");
   TTS_CHECK(resstack_x3_fits(a0, h_lens), "resstack_x3: unaligned rows, more than 64 utterances or an utterance "
@@ -556,16 +557,18 @@ void launch_resstack_x3(const StackArgs& a0, const int* h_lens, int C, hipStream
   a.ext[2] = 0;
   a.ext[1] = a.dil[2];
   a.ext[0] = a.dil[1] + a.dil[2];
+  int tq;
   if (C == 48 && a.ct16) {
     TTS_CHECK(a.xin && a.ct_bias && a.mul % 2 == 0, "resstack_x3: fused ConvTranspose arguments");
-    launch_rsx3<48, 208, 4, 4, 2>(a, h_lens, s);
+    tq = launch_rsx3<48, 208, 4, 4, 2>(a, h_lens, s);
   } else if (C == 48) {
     // 3 m-tile waves x 4 n-groups; ROWS = 240 = 15 n-tiles, <= 4 per wave
-    launch_rsx3<48, 208, 4, 4>(a, h_lens, s);
+    tq = launch_rsx3<48, 208, 4, 4>(a, h_lens, s);
   } else {
     TTS_CHECK(!a.ct16, "resstack_x3: fused ConvTranspose only at C = 48");
     // C = 96: 6 m-tile waves x 2 n-groups; ROWS = 128 = 8 n-tiles, 4 per wave (158.5 KB LDS)
-    launch_rsx3<96, 96, 2, 4>(a, h_lens, s);
+    tq = launch_rsx3<96, 96, 2, 4>(a, h_lens, s);
   }
   HIP_OK(hipGetLastError());
+  return tq;
 }
